@@ -35,6 +35,12 @@ Rank 0 prints one JSON line carrying the contract fields plus
   sustained_clock_mhz — average shader clock over the timed region (s_memtime / s_memrealtime probes);
   cpu_baseline — the reference modules (kind "reference", when /root/reference exists) or the oracle (kind
                  "port", on the GPU box) timed on this box's host cores on a bounded sample of the same workload.
+
+A plain run sets up, warms up, times the K steps and prints the line: the sub-records that take work of their own
+after the timed region (roofline.isolated, hook_path, adaptive, strong_scaling, the live roofline.traffic
+measurement, cpu_baseline) are null unless `--full` is given.  `--dump-outputs DIR` writes the last timed step's
+feature and match tables as DIR/<name>.npy (see dump_outputs); inputs and weights are seeded, so the same arguments
+give the same inputs on every run.
 """
 from __future__ import annotations
 
@@ -103,7 +109,14 @@ def parse():
     ap.add_argument("--no-live-traffic", action="store_true", help="keep roofline.traffic at the value cited from profiles/conv1b_hbm_bytes.json instead of measuring it with two "
                     "rocprofv3 --pmc passes of a one-step child run (N = 1 only; skipped when rocprofv3 is not on PATH)")
     ap.add_argument("--no-strong-scaling", action="store_true", help="skip the strong_scaling sub-record (the config-4 job run after the timed region)")
+    ap.add_argument("--full", action="store_true", help="configs2: also measure everything beyond the headline figure after the timed region — the "
+                    "isolated roofline launches, hook_path, adaptive, strong_scaling, the live roofline traffic and cpu_baseline (each still subject "
+                    "to its --no-* switch); without it those sub-records are null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="configs2: write what the last timed step computed (rank 0's feature "
+                    "and match tables) as DIR/<name>.npy, float32 / float64")
     a = ap.parse_args()
+    if a.dump_outputs is not None and a.workload != "configs2":
+        ap.error("--dump-outputs: only the configs2 workload")
     if a.images is None:
         a.images = 8 if a.workload == "config5" else 150
     if a.steps is None:
@@ -784,7 +797,7 @@ def measure_traffic_live(a, timeout_s: float = 240.0):
     """roofline.traffic of THIS run: measure_kernel_traffic over a one-step child run of this very command (same pairs per
     step = same images per launch) for the dominant kernel."""
     child = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--pairs", str(a.pairs), "--no-cpu-baseline", "--main-region-only",
-             "--no-hook-path", "--no-strong-scaling", "--no-live-traffic", "--no-adaptive"]
+             "--no-hook-path", "--no-strong-scaling", "--no-live-traffic", "--no-adaptive", "--full"]
     if a.lib:
         child += ["--lib", a.lib]
     return measure_kernel_traffic(child, "conv3x3_x6_kernel<64, 1, 1, true, 2", timeout_s)
@@ -857,6 +870,51 @@ def strong_scaling_subrun(a, rank, world, dev, dist, lib, line):
     done.set()
     if rank == 0:
         line["strong_scaling"] = strong
+
+
+DUMP_MAX_PAIRS = 256        # 172 KB of tables per pair: 256 pairs + the descriptor sample stay under 64 MB
+DUMP_DESC_ROWS = 8192
+
+
+def dump_outputs(out_dir, feats, o, n_pairs):
+    """--dump-outputs: what the last timed step handed its caller — SuperPointHIP.extract_batch's tables of the step's 2P images and
+    LightGlueHIP.match_batch's tables of its P pairs (pair p = images 2p, 2p+1) — as DIR/<name>.npy.  Floats stay float32, integer
+    tables become float64 (exact).  Entries past a count (an image's keypoints, a pair's compact match list) are written as 0 so that two
+    builds agree wherever the outputs are defined.  Above DUMP_MAX_PAIRS pairs a fixed seeded sample of pairs is written (pair_index.npy
+    names them); descriptors (1 MB per image) are a fixed seeded sample of DUMP_DESC_ROWS (image, keypoint) rows of those pairs' images."""
+    import numpy as np
+
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    kp, sc, de, n = (t.cpu() for t in feats)
+    o = {k: v.cpu() for k, v in o.items() if k in ("matches", "scores", "n_matches", "matches01", "mscores01", "stop", "prune01")}
+    pairs = torch.arange(n_pairs)
+    if n_pairs > DUMP_MAX_PAIRS:
+        pairs = torch.randperm(n_pairs, generator=torch.Generator().manual_seed(0))[:DUMP_MAX_PAIRS].sort().values
+    imgs = torch.stack([2 * pairs, 2 * pairs + 1], 1).reshape(-1)
+    kp, sc, de, n = kp[imgs], sc[imgs], de[imgs], n[imgs].long()
+    cap = sc.shape[1]
+    live = torch.arange(cap)[None] < n[:, None]                                   # [images, cap]
+    kp, sc = torch.where(live[..., None], kp, 0.0), torch.where(live, sc, 0.0)
+    rows = torch.randperm(live.numel(), generator=torch.Generator().manual_seed(1))[:DUMP_DESC_ROWS].sort().values
+    desc = torch.where(live.reshape(-1)[rows, None], de.reshape(-1, de.shape[-1])[rows], 0.0)
+    o = {k: v[pairs] for k, v in o.items()}
+    nm = o["n_matches"].long()
+    NK = o["scores"].shape[1]
+    m_live = torch.arange(NK)[None] < nm[:, None]                                 # [pairs, NK]: the compact match list
+    k_live = torch.arange(NK)[None, None] < n.view(-1, 2)[:, :, None]              # [pairs, 2, NK]: keypoints of image 0 / image 1
+    arrays = {
+        "pair_index": pairs,
+        "sp_keypoints": kp, "sp_scores": sc, "sp_n_keypoints": n,
+        "sp_descriptors_sample": desc, "sp_descriptors_sample_rows": rows,    # rows index [image of this dump, keypoint] flattened
+        "lg_matches": torch.where(m_live[..., None], o["matches"], 0), "lg_scores": torch.where(m_live, o["scores"], 0.0), "lg_n_matches": nm,
+        "lg_matches0_1": torch.where(k_live, o["matches01"], -1), "lg_mscores0_1": torch.where(k_live, o["mscores01"], 0.0),
+        "lg_prune0_1": torch.where(k_live, o["prune01"], 0), "lg_stop": o["stop"],
+    }
+    for name, t in arrays.items():
+        a = t.numpy()
+        np.save(d / f"{name}.npy", a.astype(np.float32 if a.dtype == np.float32 else np.float64))
+    return sorted(arrays)
 
 
 def main():
@@ -991,14 +1049,17 @@ def main():
     dt = time.perf_counter() - t0
     tot_ms, launches = ctypes.c_double(), ctypes.c_int()
     capi.check(lib, lib.dim_profile_stop(ctypes.byref(tot_ms), ctypes.byref(launches)))
+    if a.dump_outputs is not None and rank == 0:  # before anything below reuses the last step's buffers
+        dump_outputs(a.dump_outputs, feats[(K - 1) % 2], outs[(K - 1) % 2], P)
 
-    # the same kernel timed again with nothing else on the GPU (2 extraction-only batches after the timed region)
+    # (--full) the same kernel timed again with nothing else on the GPU (2 extraction-only batches after the timed region)
     iso_ms, iso_n = ctypes.c_double(), ctypes.c_int()
-    capi.check(lib, lib.dim_profile_start(ctypes.c_ulonglong(1 << 1)))
-    for i in range(2):
-        ext.extract_batch(pool[i % n_pool], out=feats[0])
-    torch.cuda.synchronize()
-    capi.check(lib, lib.dim_profile_stop(ctypes.byref(iso_ms), ctypes.byref(iso_n)))
+    if a.full:
+        capi.check(lib, lib.dim_profile_start(ctypes.c_ulonglong(1 << 1)))
+        for i in range(2):
+            ext.extract_batch(pool[i % n_pool], out=feats[0])
+        torch.cuda.synchronize()
+        capi.check(lib, lib.dim_profile_stop(ctypes.byref(iso_ms), ctypes.byref(iso_n)))
 
     # the other schedule over the same K steps, timed the same way (not part of `value`)
     dt2 = float("nan")
@@ -1074,7 +1135,8 @@ def main():
                          "traffic": traffic,
                          "traffic_note": "CITED, not measured by this run: HBM bytes per launch from the committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes "
                                          "of the same kernel (profiles/conv1b_hbm_bytes.json names the pass), scaled to this run's images per launch",
-                         "isolated": {"note": "same kernel, same launches, timed again right after the timed region in two extraction-only batches "
+                         "isolated": None if not a.full else {
+                                      "note": "same kernel, same launches, timed again right after the timed region in two extraction-only batches "
                                               "(the main region is single-stream, so the two agree unless --overlap is given)",
                                       "avg_launch_ms": iso_ms.value / max(1, iso_n.value),
                                       "achieved": gflop_per_launch / (iso_ms.value / max(1, iso_n.value)),
@@ -1084,23 +1146,24 @@ def main():
                          # what the launch must move: the fp32 image in, the pooled 64-channel map out as two fp16 planes (= 4 bytes per value)
                          "algorithmic_hbm_bytes_per_launch": (1024 * 1024 * 4 + 512 * 512 * 64 * 4) * 2 * P},
         }
+    # Everything below the headline figure runs with --full only.
     # the per-call plugin hooks at the headline sizes: measured before the strong-scaling sub-run, whose host-side image
     # synthesis spins up torch's CPU thread pool
-    if rank == 0 and not a.no_hook_path and not a.main_region_only:
+    if rank == 0 and a.full and not a.no_hook_path and not a.main_region_only:
         try:
             line["hook_path"] = measure_hook_path(dev, lib)
         except Exception as e:
             line["hook_path"] = {"error": repr(e)[:400]}
-    if rank == 0 and not a.no_adaptive and not a.main_region_only:
+    if rank == 0 and a.full and not a.no_adaptive and not a.main_region_only:
         try:
             line["adaptive"] = measure_adaptive(dev, lib)
         except Exception as e:
             line["adaptive"] = {"error": repr(e)[:400]}
-    if not a.no_strong_scaling and not a.main_region_only:
+    if a.full and not a.no_strong_scaling and not a.main_region_only:
         del pool, feats, flat, outs
         torch.cuda.empty_cache()
         strong_scaling_subrun(a, rank, world, dev, dist, lib, line)
-    if rank == 0 and world == 1 and not a.no_live_traffic and not a.main_region_only:
+    if rank == 0 and world == 1 and a.full and not a.no_live_traffic and not a.main_region_only:
         # after everything that is timed: two counter passes over a one-step child run (the GPU is idle, this process's batch tables are released)
         try:
             tr = measure_traffic_live(a)
@@ -1111,7 +1174,7 @@ def main():
         except Exception as e:
             line["roofline"]["traffic_measurement"] = {"error": repr(e)[:300], "fallback": "the cited value (traffic_note)"}
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(a.cpu_sample_pairs)
         else:
             line["cpu_baseline"] = None

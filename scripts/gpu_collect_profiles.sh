@@ -7,7 +7,7 @@ TAG=${1:-r01}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out
 mkdir -p $OUT
-cd $R && python bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+cd $R && python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 tail -c 600 $OUT/bench_$TAG.json
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o bench -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --main-region-only > /dev/null 2>&1
