@@ -48,12 +48,14 @@ def order_is_reference_like(out: dict, k_limited: bool):
 
 
 def compare_lightglue(out: dict, ref: dict, score_tol: float = 1e-3, dense_ref=None, dense_out=None, dense_tol: float = 1e-3,
-                      tie_tol: float = 1e-4, max_ties: int = 2, filter_threshold=None):
+                      tie_tol: float = 1e-4, max_ties: int = 2, filter_threshold=None, ind0=None, ind1=None):
     """out/ref: reference-style dicts for one pair (CPU tensors; ref from the oracle or the golden
     file).  Integer outputs (stop, prune, matches) must be identical except where the oracle's own
     decision is a numerical near-tie (two assignment scores closer than tie_tol), which is reported:
     that exception needs the oracle's dense log-assignment (dense_ref) — without it any difference fails —
-    and is bounded (at most max_ties matches, each checked by match_list_difference_is_a_tie)."""
+    and is bounded (at most max_ties matches, each checked by match_list_difference_is_a_tie).  With point pruning the oracle's
+    log-assignment lives in the pruned index space: ind0 / ind1 (the oracle's taps: the surviving keypoints of each image) map the
+    matches into it — without them a tie on a pruned case is looked up at the wrong row and column."""
     res = {}
     assert int(out["stop"]) == int(ref["stop"]), (int(out["stop"]), int(ref["stop"]))
     for k in ("prune0", "prune1"):
@@ -79,7 +81,7 @@ def compare_lightglue(out: dict, ref: dict, score_tol: float = 1e-3, dense_ref=N
         pairs_of = lambda m0: torch.stack([(m0 >= 0).nonzero().reshape(-1), m0[m0 >= 0]], 1)
         po, pr = pairs_of(a0), pairs_of(b0)
         assert {(int(j), int(i)) for i, j in po.tolist()} == {(int(j), int(i)) for j, i in pairs_of(a1).tolist()}, "matches0 / matches1 disagree"
-        ties = match_list_difference_is_a_tie(po, pr, dense_ref, 0.0 if filter_threshold is None else filter_threshold, tie_tol)
+        ties = match_list_difference_is_a_tie(po, pr, dense_ref, 0.0 if filter_threshold is None else filter_threshold, tie_tol, ind0=ind0, ind1=ind1)
         assert len(ties) <= 2 * max_ties, ties
         res["explained_near_ties"] = ties
         touched0 = {t["match"][0] for t in ties}; touched1 = {t["match"][1] for t in ties}
