@@ -52,7 +52,7 @@ def default_image_loader(path: Path, grayscale: bool = True) -> np.ndarray:
 
 
 class BatchedImageMatcher:
-    """extractor / matcher: the plugin instances of plugins.py (SuperPointExtractor, LightGlueMatcher)."""
+    """extractor / matcher: the plugin instances of plugins.py (SuperPointExtractor / AlikedExtractor, LightGlueMatcher / KorniaMatcher)."""
 
     def __init__(self, extractor, matcher, output_dir: Path, image_batch: int = 16, pair_batch: int = 16,
                  loader: Optional[Callable[[Path], np.ndarray]] = None, verify: bool = True, gv_iters: int = 2048):
@@ -175,6 +175,8 @@ class BatchedImageMatcher:
             f = feats[n]
             k = f["keypoints"].shape[0]
             kt[i, :k], dt[i, :k], nt[i], st[i] = f["keypoints"], f["descriptors"].T, k, f["image_size"].astype(np.float32)
+        if hasattr(self.mat, "_set_dim"):      # a matcher without weights (KorniaMatcher) learns the descriptor width from the features
+            self.mat._set_dim(D)
         net = self.mat._ensure_pairs(cap, self.pair_batch)
         dev = net.device
         if self._verifier is not None and net.nk > 4096:

@@ -51,6 +51,29 @@ class LgRawFeatures(ctypes.Structure):
                 ("desc_f16", ctypes.c_int), ("desc_is_dn", ctypes.c_int)]
 
 
+NN_MODES = {"nn": 0, "mnn": 1, "snn": 2, "smnn": 3}  # DIM_NN_MODE_*
+
+
+class NnConfig(ctypes.Structure):
+    """include/dim_hip.h: dim_nn_config."""
+    _fields_ = [("mode", ctypes.c_int), ("th", ctypes.c_double)]
+
+
+def declare_nn(lib) -> None:
+    """Argument / result types of the dim_nn_* entry points (idempotent; called by NearestNeighborHIP on the library it uses)."""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    lib.dim_nn_create.argtypes = [ctypes.POINTER(NnConfig), ci, ci, ci, ctypes.POINTER(vp)]
+    lib.dim_nn_create.restype = ci
+    lib.dim_nn_destroy.argtypes = [vp]
+    lib.dim_nn_destroy.restype = None
+    lib.dim_nn_max_kpts.argtypes = [vp]
+    lib.dim_nn_max_kpts.restype = ci
+    lib.dim_nn_workspace_bytes.argtypes = [vp]
+    lib.dim_nn_workspace_bytes.restype = ctypes.c_size_t
+    lib.dim_nn_match.argtypes = [vp, vp, vp, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp]
+    lib.dim_nn_match.restype = ci
+
+
 def check(lib, rc: int) -> None:
     if rc != 0:
         msg = lib.dim_last_error().decode(errors="replace")

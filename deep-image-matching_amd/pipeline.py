@@ -96,7 +96,7 @@ def _guarded(net, fn, what: str):
 
 class PairMatchingPipeline:
     """extractor: SuperPointHIP (images [n, H, W]) or AlikedHIP (images [n, H, W, C]; its descriptor width is read from the extractor: 128, 64
-    for aliked-t16), matcher: LightGlueHIP of the same input_dim (both resident on this rank's device)."""
+    for aliked-t16), matcher: LightGlueHIP or NearestNeighborHIP of the same input_dim (both resident on this rank's device)."""
 
     def __init__(self, extractor, matcher, rank: int = 0, world: int = 1):
         self.ext, self.mat, self.rank, self.world = extractor, matcher, rank, world
@@ -192,7 +192,8 @@ class PairMatchingPipeline:
                     capi.check(lib, lib.dim_op_pack_match_rows(capi.ptr(out["matches"]), capi.ptr(out["scores"]), capi.ptr(out["n_matches"]), NK, b,
                                                                 capi.ptr(rows[s:s + b]), stream()))
                 cnt[s:s + b] = out["n_matches"][:b]
-                stp[s:s + b] = out["stop"][:b]
+                if "stop" in out:      # (LightGlue's early-stop layer; a nearest-neighbour matcher has none: zeros)
+                    stp[s:s + b] = out["stop"][:b]
                 if aux:
                     prn[s:s + b] = out["prune01"][:b]
 

@@ -9,6 +9,7 @@ error behaviour, with the network replaced by the gfx950 library.  When the real
 ``MatcherBase`` (so ``extractor_loader`` / ``matcher_loader`` discover them, extractor_base.py:29-52,
 matcher_base.py:36-60); otherwise a minimal stand-in base with the same constructor contract
 (extractor_base.py:119-160) is used so the hooks can be driven and tested on their own.
+``KorniaMatcher`` mirrors matchers/kornia_matcher.py:9-53 (nearest-neighbour descriptor matching, no weights).
 See INTEGRATION.md for the module files a maintainer adds to the reference tree.
 """
 from __future__ import annotations
@@ -25,6 +26,7 @@ from . import capi
 from . import weights as _weights
 from .aliked_hip import AlikedHIP
 from .lightglue_hip import LightGlueHIP
+from .nn_hip import NearestNeighborHIP, check_mode as _check_nn_mode
 from .superpoint_hip import SuperPointHIP
 from .tile_matching import BatchedTileMatchingMixin
 from .tiling import BatchedTilingMixin
@@ -528,6 +530,129 @@ class LightGlueMatcher(BatchedTileMatchingMixin, _MatcherBase):
         with net._ctx():
             capi.run_guarded(net.lib, net._stream(), run, "LightGlue", net.on_saturation, logger, handle=net._h, arithmetic=net.arithmetic)
         torch.cuda.current_stream(dev).synchronize()
+        res = pout.numpy()
+        S = int(res[:1].view(np.int32)[0])
+        return res[2:2 + 2 * S].reshape(S, 2).copy()
+
+
+class KorniaMatcher(BatchedTileMatchingMixin, _MatcherBase):
+    """matchers/kornia_matcher.py:9 — kornia.feature.DescriptorMatcher(match_mode, th) on the gfx950 library (csrc/nn_match.hip): the matcher of the
+    shipped ``superpoint+kornia_matcher`` pipeline and of the SIFT / KeyNet / DeDoDe pipelines.  match_mode nn / mnn / snn / smnn; kornia's other
+    modes (fginn, adalam, lightglue) are rejected here, at construction.  The match list is always idx0-ascending (kornia's mnn lists by idx1 when
+    image 0 has more descriptors: the same set)."""
+
+    _default_conf = {
+        "name": "kornia_matcher",
+        "match_mode": "smnn",
+        "th": 0.8,
+    }
+    required_inputs = []
+    min_matches = 20
+    max_feat_no_tiling = 200000
+
+    def __init__(self, config) -> None:
+        super().__init__(config)
+        self._lib = capi.load()
+        self._device = _resolve_device(self._device, "KorniaMatcher")
+        cfg = {**self._default_conf, **self.config.get("matcher", {})}
+        self._mode, self._th = _check_nn_mode(cfg["match_mode"]), float(cfg["th"])
+        self._arith = _apply_arithmetic(cfg, self._lib)
+        self._on_sat = _saturation_policy(cfg)
+        self._dim = int(cfg.get("descriptor_size", 256))   # follows the features: every _match_pairs / batched call sets it (_set_dim)
+        self._net: Optional[NearestNeighborHIP] = None
+        self._net_n = 0
+
+    def _set_dim(self, dim: int) -> None:
+        self._dim = int(dim)
+
+    def _new_net(self, pairs: int, n: int) -> NearestNeighborHIP:
+        dev = self._device if isinstance(self._device, (str, torch.device)) else "cuda"
+        return NearestNeighborHIP(self._mode, self._th, dim=self._dim, max_pairs=pairs, max_kpts=n, device=dev, lib=self._lib,
+                                  on_saturation=self._on_sat, arithmetic=self._arith)
+
+    def _ensure(self, n: int):
+        if self._net is None or n > self._net_n or self._net.input_dim != self._dim:
+            # launch shapes follow the pair, not the handle, and a handle owns O(n^2 / 128) bytes: on a GPU the first one already holds 4096 rows
+            floor = 4096 if str(getattr(self._device, "type", self._device)).startswith("cuda") else 256
+            self._net_n = max(floor, 1 << (max(n, 1) - 1).bit_length())
+            self._net = self._new_net(1, self._net_n)
+
+    def _ensure_pairs(self, n: int, pairs: int):
+        """Batched instance (BatchedImageMatcher.match_pairs, tile_matching.BatchedTileMatchingMixin)."""
+        cur = getattr(self, "_net_b", None)
+        if cur is None or n > self._net_b_n or pairs > self._net_b_p or cur.input_dim != self._dim:
+            self._net_b_n = max(256, 1 << (max(n, 1) - 1).bit_length(), getattr(self, "_net_b_n", 0))
+            self._net_b_p = max(pairs, getattr(self, "_net_b_p", 0))
+            self._net_b = self._new_net(self._net_b_p, self._net_b_n)
+        return self._net_b
+
+    @torch.no_grad()
+    def _match_pairs(self, feats0: dict, feats1: dict) -> np.ndarray:
+        """feats: numpy dicts as read from features.h5; only "descriptors" is used, (D, N) as the reference stores them (KMX:36-37 transposes),
+        float16 or float32, C-contiguous or the transposed view of an (N, D) array.  Returns (S, 2) int64 index pairs (KMX:46-53).
+        One upload of the raw bytes, dim_lg_stage_features builds the fp32 (N, D) table on the device, one download of [count | list]."""
+
+        def raw(f):
+            d = f["descriptors"]
+            d = np.asarray(d[0] if isinstance(d, (list, tuple)) else d)
+            if d.ndim != 2:
+                raise ValueError(f"Invalid descriptors shape: {d.shape}")
+            if d.dtype not in (np.float16, np.float32):
+                d = d.astype(np.float32)
+            if d.T.flags.c_contiguous and not d.flags.c_contiguous:
+                return d.T, 0, d.shape[0], d.shape[1]          # the (N, D) array behind a transposed view
+            return np.ascontiguousarray(d), 1, d.shape[0], d.shape[1]
+
+        (d0, dn0, D0, m), (d1, dn1, D1, n) = raw(feats0), raw(feats1)
+        if D0 != D1 or D0 % 64 != 0:
+            raise ValueError(f"descriptor dimensions {D0} / {D1}: both images need the same width, a multiple of 64")
+        D = D0
+        self._set_dim(D)
+        self._ensure(max(m, n))
+        net = self._net
+        dev = torch.device(net.device)
+        on_gpu = dev.type == "cuda"
+        cap, NK = max(m, n, 1), net.nk
+        offs, cur = [], 256                    # raw staging: [counts 2 i32 | pad] then the two arrays at 256-byte boundaries
+        for arr in (d0, d1):
+            offs.append(cur)
+            cur += (arr.nbytes + 255) & ~255
+        st = self.__dict__.setdefault("_staging", _PinnedStaging())
+        pin = st.get("nn_in", cur)[:cur] if on_gpu else torch.empty(cur, dtype=torch.uint8)
+        h = pin.numpy()
+        h[:8].view(np.int32)[:] = (m, n)
+        for arr, o in zip((d0, d1), offs):
+            if arr.nbytes:
+                h[o:o + arr.nbytes] = arr.reshape(-1).view(np.uint8)
+        lean = self.__dict__.get("_lean")
+        tab_floats = 2 * cap * (2 + D)
+        if lean is None or lean["net"] is not net or lean["raw"].numel() < cur or lean["tab"].numel() < tab_floats:
+            flat = torch.zeros(2 + NK * 2, dtype=torch.int64, device=dev)       # [n_matches (int32) | pad | matches NK x 2]
+            out = {"matches": flat[2:].view(1, NK, 2), "scores": torch.zeros(1, NK, dtype=torch.float32, device=dev), "n_matches": flat[:1].view(torch.int32)[:1]}
+            lean = {"net": net, "raw": torch.empty(max(cur, 256 + 4 * 2 * NK * D + 1024), dtype=torch.uint8, device=dev),
+                    "tab": torch.empty(max(tab_floats, 2 * NK * (2 + D)), dtype=torch.float32, device=dev), "flat": flat, "out": out}
+            self.__dict__["_lean"] = lean
+        rawd, tab = lean["raw"], lean["tab"]
+        nbytes_out = (2 + NK * 2) * 8
+        pout = (st.get("nn_out", nbytes_out)[:nbytes_out] if on_gpu else torch.empty(nbytes_out, dtype=torch.uint8)).view(torch.int64)
+        base = rawd.data_ptr()
+        f16 = [int(d0.dtype == np.float16), int(d1.dtype == np.float16)]
+        # the staging kernel converts keypoints too; this matcher has none to give it: it reads the first 2 n descriptor values as stand-ins (into kt, unused)
+        descr = [capi.LgRawFeatures(base + offs[0], base + offs[0], m, f16[0], f16[0], dn0), capi.LgRawFeatures(base + offs[1], base + offs[1], n, f16[1], f16[1], dn1)]
+        kt, dt = tab[: 4 * cap].view(2, cap, 2), tab[4 * cap: 4 * cap + 2 * cap * D].view(2, cap, D)
+        counts = rawd[:8].view(torch.int32)
+        exact = bool(f16[0] and f16[1])      # float16 inputs: every table value has a zero low piece (one MFMA term instead of three, same bits)
+
+        def run():
+            rawd[:cur].copy_(pin, non_blocking=True)
+            capi.check(net.lib, net.lib.dim_lg_stage_features(ctypes.byref(descr[0]), ctypes.byref(descr[1]), int(cap), int(D), capi.ptr(kt), capi.ptr(dt), net._stream()))
+            net.match_batch(None, dt, counts, None, n_pairs=1, out=lean["out"], f16_exact=exact)
+            pout.copy_(lean["flat"], non_blocking=True)
+
+        with net._ctx():
+            capi.run_guarded(net.lib, net._stream(), run, "KorniaMatcher", net.on_saturation, logger, handle=net._h, arithmetic=net.arithmetic)
+        if on_gpu:
+            torch.cuda.current_stream(dev).synchronize()
         res = pout.numpy()
         S = int(res[:1].view(np.int32)[0])
         return res[2:2 + 2 * S].reshape(S, 2).copy()

@@ -302,6 +302,45 @@ int dim_lg_match(dim_lg* h, const float* kpts_tab_dev, const float* desc_tab_dev
 int dim_lg_debug_desc(dim_lg* h, const float** desc, const int32_t** n_cur, const int32_t** ind);
 
 /* ------------------------------------------------------------------------ */
+/* Nearest-neighbour descriptor matching (reference matchers/kornia_matcher.py:
+ * kornia.feature.DescriptorMatcher(match_mode, th); csrc/nn_match.hip)      */
+/* ------------------------------------------------------------------------ */
+
+/* dm = cdist(desc0, desc1) (Euclidean, from d^2 = max(|a|^2 + |b|^2 - 2 a.b, 0) with the product in the active matrix arithmetic).
+ *   nn    every row i -> (i, argmin_j dm[i]), dist = dm
+ *   mnn   (i, j) with j = argmin dm[i, :] and i = argmin dm[:, j], dist = dm
+ *   snn   rows with d_best / d_second <= th (needs N >= 2), dist = the ratio
+ *   smnn  snn(0 -> 1) intersected with the flipped snn(1 -> 0) (needs M, N >= 2), dist = the larger ratio
+ * Ties on equal distances go to the lowest index; a 0 / 0 ratio is no match; too few descriptors give an empty list.  The list is always
+ * idx0-ascending (kornia's mnn lists by idx1 when M > N: same set). */
+enum { DIM_NN_MODE_NN = 0, DIM_NN_MODE_MNN, DIM_NN_MODE_SNN, DIM_NN_MODE_SMNN };
+typedef struct dim_nn_config {
+  int mode;    /* DIM_NN_MODE_* */
+  double th;   /* ratio threshold of snn / smnn (compared in fp32) */
+} dim_nn_config;
+typedef struct dim_nn dim_nn;
+/* dim: descriptor dimension, a multiple of 64 (64, 128, 256). */
+int dim_nn_create(const dim_nn_config* cfg, int max_pairs, int max_kpts, int dim, dim_nn** out);
+void dim_nn_destroy(dim_nn* h);
+/* Row stride (>= max_kpts, multiple of 4) of the per-pair output arrays below. */
+int dim_nn_max_kpts(dim_nn* h);
+/* Device bytes the handle owns: squared norms, per-tile partial (min, argmin, second) triples, final triples — O(max_kpts^2 / 128) per
+ * pair; the max_kpts x max_kpts distance matrix is never stored. */
+size_t dim_nn_workspace_bytes(dim_nn* h);
+/* Matches n_pairs pairs of a device feature table desc_tab_dev [n_img][cap][dim] fp32 (row-major (N, D)), n_tab_dev [n_img]; pair_idx_dev
+ * [n_pairs][2] int32 = image slots of (image0, image1), NULL = pair p is slots (2p, 2p+1).  Counts above the handle's max_kpts are truncated.
+ * desc_is_f16_exact != 0: the caller states that every table value is exactly representable in float16 (what features.h5 stores) — under
+ * fp16x3 one MFMA term runs instead of three, with bit-identical results on such tables.
+ * Outputs (device, caller allocated; NK = dim_nn_max_kpts(h)), the layout of dim_lg_match:
+ *   matches_dev [n_pairs][NK][2] int64 compact (idx0, idx1) list, idx0 ascending;  dists_dev [n_pairs][NK];  n_matches_dev [n_pairs].
+ * row_stats_dev / col_stats_dev: NULL, or parity taps [n_pairs][3][NK] (4-byte elements): plane 0 = argmin index (int32), plane 1 = min d^2,
+ * plane 2 = second-smallest d^2 (fp32), per descriptor of image0 over image1 / of image1 over image0.
+ * Inputs with |x| > 4094 under fp16x3 bump the DIM_SAT_OP counter (dim_saturation_read).  The call only enqueues work on `stream`. */
+int dim_nn_match(dim_nn* h, const float* desc_tab_dev, const int32_t* n_tab_dev, int cap, int desc_is_f16_exact, const int32_t* pair_idx_dev,
+                 int n_pairs, int64_t* matches_dev, float* dists_dev, int32_t* n_matches_dev, float* row_stats_dev, float* col_stats_dev,
+                 void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* operator-level entry points (each is one kernel launch; used by the      */
 /* parity tests and available to integrators)                               */
 /* ------------------------------------------------------------------------ */
