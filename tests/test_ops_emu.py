@@ -3,72 +3,47 @@ import ctypes
 
 import pytest
 import torch
-import torch.nn.functional as F
 
-from oracle import superpoint_ref
-
-
-def p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+from tests import op_cases
+from tests.op_cases import _ffn_fused_case, _ffn_ln_gelu_case, p  # noqa: F401  (tests/test_lightglue_gpu.py imports the two cases from here)
 
 
 @pytest.mark.parametrize("radius", [0, 1, 2, 3, 4, 5, 6])
 def test_simple_nms_bit_exact_with_ties_and_plateaus(emu_lib, radius):
-    g = torch.Generator().manual_seed(radius)
-    H, W = 45, 70  # not multiples of the tile; includes the image border logic
-    s = torch.rand(2, H, W, generator=g)
-    s[0] = (s[0] * 6).round() / 6 + 0.01  # heavy ties / plateaus (SURVEY App. D KATs)
-    s[1, 10:20, 10:30] = 0.5
-    out = torch.full_like(s, -1.0)
-    assert emu_lib.dim_op_simple_nms_f32(p(s), p(out), 2, H, W, radius, None) == 0, emu_lib.dim_last_error()
-    ref = superpoint_ref.simple_nms(s, radius)
-    assert torch.equal(out, ref)
+    r = op_cases.nms_case(emu_lib, op_cases.nms_tie_map(radius), radius)   # 45 x 70: not multiples of the tile; includes the image border logic
+    assert torch.equal(r.out, r.ref) and r.guard_ok
 
 
 @pytest.mark.parametrize("radius", [1, 3, 4])
 def test_simple_nms_64_tiles_bit_exact(emu_lib, radius):
     """The 64 x 64-tile variant (dim_tune_set key 7 = 2 forces it on any map size) on a map with partial tiles on both axes."""
-    g = torch.Generator().manual_seed(40 + radius)
-    H, W = 75, 130
-    s = torch.rand(1, H, W, generator=g)
-    s[0, :40] = (s[0, :40] * 5).round() / 5 + 0.01
-    s[0, 50:70, 60:100] = 0.5
-    out = torch.full_like(s, -1.0)
     try:
         emu_lib.dim_tune_set(7, 2)
-        assert emu_lib.dim_op_simple_nms_f32(p(s), p(out), 1, H, W, radius, None) == 0, emu_lib.dim_last_error()
+        r = op_cases.nms_case(emu_lib, op_cases.nms_partial_tile_map(radius), radius)
     finally:
         emu_lib.dim_tune_set(7, 1)
-    assert torch.equal(out, superpoint_ref.simple_nms(s, radius))
+    assert torch.equal(r.out, r.ref) and r.guard_ok
 
 
 @pytest.mark.parametrize("M,N,K,bt", [(200, 65, 64, 0), (130, 256, 256, 0), (150, 140, 64, 1), (1, 4, 32, 0)])
 def test_gemm_mfma(emu_lib, M, N, K, bt):
-    g = torch.Generator().manual_seed(M)
-    A = torch.randn(M, K, generator=g)
-    B = torch.randn(N, K, generator=g) if bt else torch.randn(K, ((N + 3) // 4) * 4, generator=g)
-    bias, R = torch.randn(N, generator=g), torch.randn(M, N, generator=g)
-    C = torch.zeros(M, N)
-    assert emu_lib.dim_op_gemm_f32(p(A), K, p(B), B.shape[1], bt, p(bias), p(R), N, p(C), N, M, N, K, 1, None) == 0
-    ref = torch.relu((A @ B.T if bt else A @ B[:, :N]) + bias + R)
-    assert (C - ref).abs().max() < 1e-4
+    r = op_cases.gemm_f32_case(emu_lib, M, N, K, bt)
+    assert r.abs_err.max() < 1e-4 and r.guard_ok
 
 
 @pytest.mark.parametrize("cin,cout,H,W,pool", [(64, 64, 20, 37, 1), (64, 128, 9, 33, 0), (128, 128, 16, 34, 1)])
 def test_conv3x3_mfma(emu_lib, cin, cout, H, W, pool):
-    g = torch.Generator().manual_seed(cin + H)
-    x = torch.randn(2, cin, H, W, generator=g)
-    w = torch.randn(cout, cin, 3, 3, generator=g) * 0.1
-    b = torch.randn(cout, generator=g)
-    xin = x.permute(0, 2, 3, 1).contiguous()
-    wk = w.permute(2, 3, 1, 0).contiguous().reshape(9, cin, cout)
-    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
-    out = torch.full((2, Ho, Wo, cout), -7.0)
-    assert emu_lib.dim_op_conv3x3_nhwc_f32(p(xin), p(wk), p(b), p(out), 2, H, W, cin, cout, pool, 1, None) == 0
-    ref = torch.relu(F.conv2d(x, w, b, padding=1))
-    if pool:
-        ref = F.max_pool2d(ref, 2, 2)
-    assert (out - ref.permute(0, 2, 3, 1)).abs().max() < 1e-4
+    r = op_cases.conv3x3_case(emu_lib, cin, cout, H, W, pool)
+    assert r.abs_err.max() < 1e-4 and r.guard_ok
+
+
+@pytest.mark.parametrize("batch,H,W", [(2, 45, 70)])
+def test_conv1a_vs_fp64(emu_lib, batch, H, W):
+    """conv1a_kernel (1 -> 64 channels, direct VALU convolution; 64-pixel row segments, so W = 70 leaves a ragged second block) against fp64 conv2d + ReLU.
+    Bound: an image in [0, 1] and weights of order 0.3 give sums of a few units; nine fmas and a bias add round at most ten times at <= 2^-22 each:
+    1e-5 absolute is derived, not measured."""
+    r = op_cases.conv1a_case(emu_lib, batch, H, W)
+    assert r.abs_err.max() < 1e-5 and r.guard_ok
 
 
 @pytest.fixture(params=[2, 1], ids=["fp16x3", "bf16x6"])
@@ -83,39 +58,39 @@ def split_mode(request, emu_lib):
 def test_gemm_split_precision_is_fp32_accurate(emu_lib, split_mode, M, N, K):
     """bf16x6 (exact 3-way bf16 split, six cross terms) and fp16x3 (2-way fp16 split of the scaled operands,
     three cross terms) on the 16-bit MFMA == fp32-class accuracy (vs fp64)."""
-    g = torch.Generator().manual_seed(K + M)
-    A, W = torch.randn(M, K, generator=g), torch.randn(K, N, generator=g).contiguous()
-    bias, R = torch.randn(N, generator=g), torch.randn(M, N, generator=g)
-    C = torch.zeros(M, N)
-    dev, npad = ctypes.c_void_p(), ctypes.c_int()
-    assert emu_lib.dim_x3_create(p(W), K, N, ctypes.byref(dev), ctypes.byref(npad)) == 0
-    assert emu_lib.dim_op_gemm_x6_f32(p(A), K, dev, npad.value, p(bias), p(R), N, p(C), N, M, N, K, 0, None) == 0, emu_lib.dim_last_error()
-    emu_lib.dim_x3_destroy(dev)
-    ref = (A.double() @ W.double() + bias.double() + R.double())
-    mag = (A.abs().double() @ W.abs().double())
-    assert ((C.double() - ref).abs() / mag).max().item() < 4e-7
+    r = op_cases.gemm_x6_case(emu_lib, M, N, K)
+    assert r.rel_err < 4e-7 and r.guard_ok
+
+
+@pytest.mark.parametrize("M,N,K", [(200, 65, 96), (200, 65, 128), (70, 130, 256), (70, 130, 512)])
+def test_gemm_small_problem_kernels_are_fp32_accurate(emu_lib, M, N, K):
+    """The four small-problem fp16x3 kernels of launch_gemm_x6 (at most 512 workgroups of 64 rows): K = 96 -> gemm_x6_kernel<2,32,1,4> (K % 128 != 0),
+    K = 128 -> gemm_x6_small32_kc64_kernel<true> (run-time K), K = 256 / 512 -> its <true,256> / <true,512> instances; ragged in M and N."""
+    r = op_cases.gemm_x6_case(emu_lib, M, N, K, act=1)
+    assert r.rel_err < 4e-7 and r.guard_ok
+
+
+@pytest.mark.parametrize("bias,residual", [(True, True), (False, False)])
+def test_gemm_selu_epilogue(emu_lib, bias, residual):
+    """act = 2 (SELU, what ALIKED uses) at (200, 65, 64): the pre-activation error bound times SELU's Lipschitz constant plus 4 ulp for expf (op_cases.selu_bound)."""
+    r = op_cases.gemm_x6_case(emu_lib, 200, 65, 64, act=2, bias=bias, residual=residual)
+    assert bool((r.abs_err <= op_cases.selu_bound(r.scale)).all()) and r.guard_ok
+    assert bool((r.ref < 0).any()) and bool((r.ref > 0).any())          # both branches of the activation are exercised
 
 
 @pytest.mark.parametrize("M,N,K", [(130, 256, 512), (200, 500, 64)])
 def test_gemm_wide_blocks_are_bit_identical(emu_lib, M, N, K):
     """The 128 x 256 workgroup block of gemm_x6.hip (dim_tune_set key 6; 2 = forced whatever the problem size) accumulates
     every output in the same order as the 128 x 128 block."""
-    g = torch.Generator().manual_seed(K + M)
-    A, W = torch.randn(M, K, generator=g), torch.randn(K, N, generator=g).contiguous()
-    bias, R = torch.randn(N, generator=g), torch.randn(M, N, generator=g)
-    dev, npad = ctypes.c_void_p(), ctypes.c_int()
-    assert emu_lib.dim_x3_create(p(W), K, N, ctypes.byref(dev), ctypes.byref(npad)) == 0
     outs = []
     try:
         for wide in (0, 2):
             emu_lib.dim_tune_set(6, wide)
-            C = torch.full((M, N), -3.0)
-            assert emu_lib.dim_op_gemm_x6_f32(p(A), K, dev, npad.value, p(bias), p(R), N, p(C), N, M, N, K, 1, None) == 0, emu_lib.dim_last_error()
-            outs.append(C)
+            outs.append(op_cases.gemm_x6_case(emu_lib, M, N, K, act=1))
     finally:
         emu_lib.dim_tune_set(6, 1)
-        emu_lib.dim_x3_destroy(dev)
-    assert torch.equal(outs[0], outs[1])
+    assert torch.equal(outs[0].raws[0], outs[1].raws[0]) and outs[0].guard_ok and outs[1].guard_ok
+    assert bool((outs[0].out != op_cases.SENTINEL).all())
 
 
 @pytest.mark.parametrize("M,N,K", [(130, 256, 512), (200, 500, 64), (70, 128, 256)])
@@ -143,22 +118,8 @@ def test_gemm_streaming_k_loop_prototype_is_bit_identical(emu_research_lib, M, N
 
 @pytest.mark.parametrize("cin,cout,H,W,pool", [(64, 64, 20, 37, 1), (64, 128, 9, 33, 0), (128, 128, 16, 34, 1)])
 def test_conv3x3_split_precision_is_fp32_accurate(emu_lib, split_mode, cin, cout, H, W, pool):
-    g = torch.Generator().manual_seed(cin + H)
-    x = torch.randn(2, cin, H, W, generator=g)
-    w = (torch.randn(cout, cin, 3, 3, generator=g) * 0.1).contiguous()
-    b = torch.randn(cout, generator=g)
-    xin = x.permute(0, 2, 3, 1).contiguous()
-    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
-    out = torch.full((2, Ho, Wo, cout), -7.0)
-    dev = ctypes.c_void_p()
-    assert emu_lib.dim_convx6_create(p(w), cin, cout, ctypes.byref(dev)) == 0
-    assert emu_lib.dim_op_conv3x3_x6_nhwc_f32(p(xin), dev, p(b), p(out), 2, H, W, cin, cout, pool, 1, None) == 0
-    emu_lib.dim_x3_destroy(dev)
-    ref = torch.relu(F.conv2d(x.double(), w.double(), b.double(), padding=1))
-    if pool:
-        ref = F.max_pool2d(ref, 2, 2)
-    mag = F.conv2d(x.abs().double(), w.abs().double(), padding=1).max().item()
-    assert (out.double() - ref.permute(0, 2, 3, 1)).abs().max().item() / mag < 4e-7
+    r = op_cases.conv3x3_case(emu_lib, cin, cout, H, W, pool, split=True)
+    assert r.rel_err < 4e-7 and r.guard_ok
 
 
 @pytest.mark.parametrize("regime", ["tiny", "large", "overflow"])
@@ -183,57 +144,11 @@ def test_fp16x3_range_behaviour(emu_lib, regime):
         assert ((C.double() - ref).abs() / mag).max().item() < (2e-6 if regime == "tiny" else 4e-7)
 
 
-def _ffn_ln_gelu_case(lib, M, K, seed, device="cpu"):
-    """gelu(layer_norm(A W + b)) through dim_op_gemm_x6_ln_gelu_f32 -> (device result, fp64 reference)."""
-    g = torch.Generator().manual_seed(seed)
-    A = torch.randn(M, K, generator=g) * 1.5
-    W = (torch.randn(K, 512, generator=g) / K ** 0.5).contiguous()
-    bias, gamma, beta = torch.randn(512, generator=g) * 0.1, 1.0 + 0.2 * torch.randn(512, generator=g), 0.1 * torch.randn(512, generator=g)
-    dev, npad = ctypes.c_void_p(), ctypes.c_int()
-    assert lib.dim_x3_create(p(W), K, 512, ctypes.byref(dev), ctypes.byref(npad)) == 0 and npad.value == 512
-    Ad, bd, gd, btd = (t.to(device).contiguous() for t in (A, bias, gamma, beta))
-    C = torch.full((M, 512), -7.0, device=device)
-    try:
-        rc = lib.dim_op_gemm_x6_ln_gelu_f32(p(Ad), K, dev, p(bd), p(gd), p(btd), p(C), 512, M, K, None)
-        assert rc == 0, lib.dim_last_error()
-        if device != "cpu":
-            torch.cuda.synchronize()
-    finally:
-        lib.dim_x3_destroy(dev)
-    h = A.double() @ W.double() + bias.double()
-    ref = torch.nn.functional.gelu(torch.nn.functional.layer_norm(h, (512,), gamma.double(), beta.double(), 1e-5))
-    return C.cpu(), ref
-
-
 @pytest.mark.parametrize("M,K", [(64, 512), (150, 512), (67, 256)])
 def test_ffn_layernorm_gelu_fused_op_vs_fp64(emu_lib, M, K):
     """LightGlue's ffn.0 -> LayerNorm -> GELU as one kernel (64 x 512 blocks; ragged last block) against an fp64 evaluation."""
     C, ref = _ffn_ln_gelu_case(emu_lib, M, K, seed=M + K)
     assert (C.double() - ref).abs().max().item() < 5e-6
-
-
-def _ffn_fused_case(lib, M, K, seed, device="cpu"):
-    """residual + gelu(layer_norm(A W0 + b0)) W3 + b3 through dim_op_ffn_fused_f32 -> (device result, fp64 reference)."""
-    g = torch.Generator().manual_seed(seed)
-    A = torch.randn(M, K, generator=g) * 1.5
-    W0 = (torch.randn(K, 512, generator=g) / K ** 0.5).contiguous()
-    W3 = (torch.randn(512, 256, generator=g) / 512 ** 0.5).contiguous()
-    b0, gamma, beta = torch.randn(512, generator=g) * 0.1, 1.0 + 0.2 * torch.randn(512, generator=g), 0.1 * torch.randn(512, generator=g)
-    b3, R = torch.randn(256, generator=g) * 0.1, torch.randn(M, 256, generator=g)
-    h0, h3, npad = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int()
-    assert lib.dim_x3_create(p(W0), K, 512, ctypes.byref(h0), ctypes.byref(npad)) == 0 and npad.value == 512
-    assert lib.dim_x3_create_kperm(p(W3), 512, 256, ctypes.byref(h3), ctypes.byref(npad)) == 0 and npad.value == 256
-    Ad, b0d, gd, btd, b3d, Rd = (t.to(device).contiguous() for t in (A, b0, gamma, beta, b3, R))
-    C = torch.full((M, 256), -7.0, device=device)
-    try:
-        rc = lib.dim_op_ffn_fused_f32(p(Ad), K, h0, p(b0d), p(gd), p(btd), h3, p(b3d), p(Rd), 256, p(C), 256, M, K, None)
-        assert rc == 0, lib.dim_last_error()
-        if device != "cpu":
-            torch.cuda.synchronize()
-    finally:
-        lib.dim_x3_destroy(h0); lib.dim_x3_destroy(h3)
-    h = torch.nn.functional.gelu(torch.nn.functional.layer_norm(A.double() @ W0.double() + b0.double(), (512,), gamma.double(), beta.double(), 1e-5))
-    return C.cpu(), R.double() + h @ W3.double() + b3.double()
 
 
 @pytest.mark.parametrize("M,K", [(64, 512), (150, 512), (67, 256)])
@@ -247,16 +162,9 @@ def test_ffn_fused_op_vs_fp64(emu_lib, M, K):
 def test_gemm_x6_nt_vs_fp64(emu_lib, M, N, K):
     """sim = A B^T with both operands split on the fly (gemm_x6_nt_kernel, LightGlue's similarity) vs fp64; ragged last blocks; a
     guard band around C stays untouched."""
-    g = torch.Generator().manual_seed(M + N)
-    A, B = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g)
-    ldc = N + 8
-    C = torch.full((M + 3, ldc), -7.0)
-    rc = emu_lib.dim_op_gemm_x6_nt_f32(p(A), K, p(B), K, p(C), ldc, M, N, K, None)
-    assert rc == 0, emu_lib.dim_last_error()
-    ref = A.double() @ B.double().t()
-    scale = (A.double().abs() @ B.double().abs().t())
-    assert ((C[:M, :N].double() - ref).abs() / scale).max().item() < 5e-7
-    assert bool((C[M:] == -7.0).all()) and bool((C[:, N:] == -7.0).all())
+    r = op_cases.gemm_x6_nt_case(emu_lib, M, N, K)
+    assert r.rel_err < 5e-7
+    assert r.guard_ok
 
 
 @pytest.mark.parametrize("kf16,df16,dn", [(0, 0, 0), (1, 1, 1), (0, 1, 0), (1, 0, 1)])

@@ -1,0 +1,193 @@
+"""GPU: the operator-level entry points (dim_op_* of include/dim_hip.h) of the matrix-core, convolution and NMS kernels ON HARDWARE against fp64 (NMS:
+bit-exact against the oracle), through the builders of tests/op_cases.py that the emulator tests use.
+
+The emulator has no memory model, no caches and no timing: workgroups run one after another and fibers in a fixed order between barriers.  A missing
+barrier around an LDS restage or a missing wait after an LDS-DMA is invisible there and shows on hardware only when two workgroups share a CU (the
+recorded case: test_lightglue_gpu.test_ffn_layernorm_gelu_fused_op_at_production_rows).  So every kernel gets
+  * a small ragged shape (partial last blocks on every axis), and
+  * an occupancy shape: the smallest one with >= 512 workgroups (two per CU on 256 CUs) that still has a ragged tail, with K small so that the fp64
+    reference stays around a second;
+every case runs TWICE on the same inputs and must give the same bits, stay within the bound the emulator test asserts for the operator, and leave the
+guard band around its output (op_cases.py) untouched.
+
+Case -> kernel (from launch_gemm / launch_gemm_x6 / launch_gemm_x6_nt / launch_conv3x3 / launch_conv3x3_x6 / launch_conv1a / launch_nms; wg = workgroups):
+
+  test_gemm_f32                (200,65,64) (130,256,256) (1,4,32)           gemm_mfma_kernel<0>          4 / 4 / 1 wg
+                               (150,140,64) b_is_nk                         gemm_mfma_kernel<1>          4 wg
+                               (65573,128,64), and b_is_nk                  gemm_mfma_kernel<0> / <1>    513 wg
+  test_gemm_x6_fp16x3          (4101,768,256)                               gemm_x6_small32_kc64_kernel<true,256>    129 x 6 = 774 wg
+                               (4101,768,512)                               gemm_x6_small32_kc64_kernel<true,512>    774 wg
+                               (4101,768,128)                               gemm_x6_small32_kc64_kernel<true,0>      774 wg
+                               (4101,768,96)                                gemm_x6_kernel<2,32,1,4>                 774 wg
+                               (65573,65,256)   n_pad 128: never wide       gemm_x6_kernel<2,128,2,2>                513 wg
+                               (200,65,64) (64,130,32)                      gemm_x6_kernel<2,32,1,4>                 7 / 4 wg
+                               (130,256,512)                                gemm_x6_small32_kc64_kernel<true,512>    10 wg
+  test_gemm_x6_large_blocks    (32805,256,64)  key 6 = 0                    gemm_x6_kernel<2,128,2,2>                257 x 2 = 514 wg
+                                               key 6 = 2 (forced)           gemm_x6_kernel<2,128,2,4>                257 wg
+                               (65573,256,64)  key 6 = 1 (natural: 513 >= 512 wide blocks)  gemm_x6_kernel<2,128,2,4>   513 wg
+                                               key 6 = 0                    gemm_x6_kernel<2,128,2,2>                1026 wg
+  test_gemm_x6_bf16x6          (200,65,64)                                  gemm_x6_kernel<1,64,2,2>                 4 wg
+                               (65573,128,64)                               gemm_x6_kernel<1,128,2,2>                513 wg
+  test_gemm_x6_nt              (150,200,256) (128,128,64) (37,300,256)      gemm_x6_nt_kernel<2> / <1>               4 / 1 / 3 wg
+                               (2085,4101,64)                               gemm_x6_nt_kernel<2> / <1>               17 x 33 = 561 wg
+  test_conv3x3_f32             three small shapes, batch 2, key 0 = 1..4    conv3x3_mfma_kernel<cin,pool,8,0,3> / <..,8,1,2> / <..,8,1,3> / <..,16,0,1>
+                               64 -> 256 130 x 250, 128 -> 128 130 x 490 (pool 0 / 1), key 0 = 3      conv3x3_mfma_kernel<cin,pool,8,1,3>   544 wg
+  test_conv3x3_x6_fp16x3       the same seven shapes                        conv3x3_x6_kernel<cin,pool,1,false,2,false,false>
+  test_conv3x3_x6_bf16x6       the same seven shapes, key 2 = 0 / 1 / 2     conv3x3_x6_kernel<cin,pool,0 / 1 / 2,false,1,false,false>
+  test_conv1a                  (2,45,70) / (2,130,150)                      conv1a_kernel                180 / 780 wg
+  test_nms_small_maps          radius 0: nms_kernel<0,32,512,8>; 2: <2,32,..>; 5, 6: <5|6,16,512,8>; radius 1, 3, 4: key 7 = 0 nms_kernel<r,32,512,8>,
+                               key 7 = 2 nms_kernel<1,64,1024,8> / <3,64,1024,10> / <4,64,1024,12>
+  test_nms_large_map           4 x 500 x 500, 8 * 8 * 4 = 256 tiles: the 64-tile kernels by themselves under key 7 = 1, the 32-tile ones under key 7 = 0
+
+launch_gemm_x6's gemm_x6_kernel<2,64,2,2> branch is not in the table: a small problem has cdiv(M,128) * cdiv(N,128) < 256 workgroups, so at most
+2 * 255 = 510 workgroups of 64 rows, which is never above the 512 that the branch before it accepts.
+"""
+import contextlib
+
+import pytest
+import torch
+
+from tests import op_cases
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+TUNE_DEFAULTS = {0: 3, 1: 2, 2: 17, 6: 1, 7: 1}
+
+
+@contextlib.contextmanager
+def tuned(lib, keys):
+    """dim_tune_set(key, value) for the duration of a case; the defaults come back whatever happens."""
+    try:
+        for k, v in keys.items():
+            assert lib.dim_tune_set(k, v) == 0, lib.dim_last_error()
+        yield
+    finally:
+        for k in keys:
+            lib.dim_tune_set(k, TUNE_DEFAULTS[k])
+
+
+def check(r, figure, bound):
+    """Same bits run to run, an intact guard band, and the accuracy figure (printed before it is asserted) within the bound."""
+    print(f"figure {figure:.4g} bound {bound:.4g} repeatable {r.repeatable} guard_ok {r.guard_ok}")
+    assert r.repeatable, "two runs on the same inputs differ"
+    assert r.guard_ok, "the guard band around the output was written"
+    assert figure < bound
+
+
+def check_gemm_x6(r, act):
+    if act == 2:   # SELU: elementwise (op_cases.selu_bound); the figure is the largest ratio to it
+        check(r, (r.abs_err / op_cases.selu_bound(r.scale)).max().item(), 1.0 + 1e-12)
+        assert bool((r.ref < 0).any()) and bool((r.ref > 0).any())
+    else:
+        check(r, r.rel_err, 4e-7)
+
+
+# ---------------------------------------------------------------------------------------------------------------- GEMM
+@pytest.mark.parametrize("M,N,K,bt", [(200, 65, 64, 0), (130, 256, 256, 0), (150, 140, 64, 1), (1, 4, 32, 0), (65573, 128, 64, 0), (65573, 128, 64, 1)])
+def test_gemm_f32(hip_lib, M, N, K, bt):
+    r = op_cases.gemm_f32_case(hip_lib, M, N, K, bt, device=DEV, runs=2)
+    check(r, r.abs_err.max().item(), 1e-4)
+
+
+@pytest.mark.parametrize("M,N,K,act,bias,residual", [
+    (4101, 768, 256, 0, True, True),
+    (4101, 768, 512, 1, True, False),
+    (4101, 768, 128, 2, False, True),
+    (4101, 768, 96, 1, False, False),
+    (65573, 65, 256, 2, True, False),
+    (200, 65, 64, 0, True, True),
+    (200, 65, 64, 2, True, True),
+    (130, 256, 512, 0, True, True),
+    (64, 130, 32, 0, True, True),
+])
+def test_gemm_x6_fp16x3(hip_lib, M, N, K, act, bias, residual):
+    r = op_cases.gemm_x6_case(hip_lib, M, N, K, act=act, bias=bias, residual=residual, device=DEV, runs=2)
+    check_gemm_x6(r, act)
+
+
+@pytest.mark.parametrize("M,N,K,key6,other", [(32805, 256, 64, 0, 2), (65573, 256, 64, 1, 0)])
+def test_gemm_x6_large_blocks(hip_lib, M, N, K, key6, other):
+    """The large-problem 128 x 128 and 128 x 256 blocks at two workgroups per CU, and the same shape forced to the other block: bit-identical (the hardware
+    counterpart of test_ops_emu.test_gemm_wide_blocks_are_bit_identical)."""
+    with tuned(hip_lib, {6: key6}):
+        r = op_cases.gemm_x6_case(hip_lib, M, N, K, act=1, device=DEV, runs=2)
+    with tuned(hip_lib, {6: other}):
+        o = op_cases.gemm_x6_case(hip_lib, M, N, K, act=1, device=DEV, runs=1)
+    check_gemm_x6(r, 1)
+    check_gemm_x6(o, 1)
+    assert torch.equal(r.raws[0], o.raws[0]), "the 128 x 128 and the 128 x 256 block differ"
+
+
+@pytest.mark.parametrize("M,N,K", [(200, 65, 64), (65573, 128, 64)])
+def test_gemm_x6_bf16x6(hip_lib, M, N, K):
+    with tuned(hip_lib, {1: 1}):
+        r = op_cases.gemm_x6_case(hip_lib, M, N, K, device=DEV, runs=2)
+    check_gemm_x6(r, 0)
+
+
+@pytest.mark.parametrize("mode", [2, 1], ids=["fp16x3", "bf16x6"])
+@pytest.mark.parametrize("M,N,K", [(150, 200, 256), (128, 128, 64), (37, 300, 256), (2085, 4101, 64)])
+def test_gemm_x6_nt(hip_lib, M, N, K, mode):
+    with tuned(hip_lib, {1: mode}):
+        r = op_cases.gemm_x6_nt_case(hip_lib, M, N, K, device=DEV, runs=2)
+    check(r, r.rel_err, 5e-7)
+
+
+# ---------------------------------------------------------------------------------------------------------------- convolutions
+SMALL_CONV = [(64, 64, 20, 37, 1, 2), (64, 128, 9, 33, 0, 2), (128, 128, 16, 34, 1, 2)]                                # (cin, cout, H, W, pool, batch): the emulator's shapes
+BIG_CONV = [(64, 256, 130, 250, 0, 1), (64, 256, 130, 250, 1, 1), (128, 128, 130, 490, 0, 1), (128, 128, 130, 490, 1, 1)]  # cdiv(W,32) * cdiv(H,8) * cout/64 = 544 workgroups
+# (shape-major order everywhere below: consecutive cases share one cached fp64 reference)
+
+
+@pytest.mark.parametrize("shape,variant", [(s, v) for s in SMALL_CONV for v in (1, 2, 3, 4)] + [(s, 3) for s in BIG_CONV])
+def test_conv3x3_f32(hip_lib, shape, variant):
+    cin, cout, H, W, pool, batch = shape
+    with tuned(hip_lib, {0: variant}):
+        r = op_cases.conv3x3_case(hip_lib, cin, cout, H, W, pool, batch=batch, device=DEV, runs=2)
+    check(r, r.abs_err.max().item(), 1e-4)
+
+
+@pytest.mark.parametrize("shape", SMALL_CONV + BIG_CONV)
+def test_conv3x3_x6_fp16x3(hip_lib, shape):
+    cin, cout, H, W, pool, batch = shape
+    r = op_cases.conv3x3_case(hip_lib, cin, cout, H, W, pool, batch=batch, split=True, device=DEV, runs=2)
+    check(r, r.rel_err, 4e-7)
+
+
+@pytest.mark.parametrize("shape,prefetch", [(s, v) for s in SMALL_CONV + BIG_CONV for v in (0, 1, 2)])
+def test_conv3x3_x6_bf16x6(hip_lib, shape, prefetch):
+    cin, cout, H, W, pool, batch = shape
+    with tuned(hip_lib, {1: 1, 2: prefetch}):
+        r = op_cases.conv3x3_case(hip_lib, cin, cout, H, W, pool, batch=batch, split=True, device=DEV, runs=2)
+    check(r, r.rel_err, 4e-7)
+
+
+@pytest.mark.parametrize("batch,H,W", [(2, 45, 70), (2, 130, 150)])
+def test_conv1a(hip_lib, batch, H, W):
+    """1e-5 absolute: derived in test_ops_emu.test_conv1a_vs_fp64 (nine fmas and a bias on an image in [0, 1], weights of order 0.3)."""
+    r = op_cases.conv1a_case(hip_lib, batch, H, W, device=DEV, runs=2)
+    check(r, r.abs_err.max().item(), 1e-5)
+
+
+# ---------------------------------------------------------------------------------------------------------------- simple_nms
+@pytest.mark.parametrize("key7", [0, 2])
+@pytest.mark.parametrize("radius", [0, 1, 2, 3, 4, 5, 6])
+@pytest.mark.parametrize("make_map", [op_cases.nms_tie_map, op_cases.nms_partial_tile_map], ids=["ties45x70", "partial75x130"])
+def test_nms_small_maps(hip_lib, make_map, radius, key7):
+    with tuned(hip_lib, {7: key7}):
+        r = op_cases.nms_case(hip_lib, make_map(radius), radius, device=DEV, runs=2)
+    assert r.repeatable and r.guard_ok
+    assert torch.equal(r.out, r.ref)
+
+
+@pytest.mark.parametrize("radius", [1, 2, 3, 4, 6])
+def test_nms_large_map(hip_lib, radius):
+    """256 tiles of 64 x 64: launch_nms takes the 64-tile kernel by itself (radius 1, 3, 4); key 7 = 0 keeps 32-tile workgroups (1024 of them).  Both == the oracle."""
+    s = op_cases.nms_large_map()
+    r = op_cases.nms_case(hip_lib, s, radius, device=DEV, runs=2)
+    with tuned(hip_lib, {7: 0}):
+        o = op_cases.nms_case(hip_lib, s, radius, device=DEV, runs=2)
+    assert r.repeatable and r.guard_ok and o.repeatable and o.guard_ok
+    assert torch.equal(r.out, r.ref) and torch.equal(o.out, r.ref)
+    assert 0 < int((r.ref > 0).sum()) < r.ref.numel() // 2
