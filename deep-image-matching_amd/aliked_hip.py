@@ -47,62 +47,29 @@ class _AlConfig(ctypes.Structure):
                [("detection_threshold", ctypes.c_double), ("nms_radius", ctypes.c_int)]
 
 
-class AlikedHIP:
+class AlikedHIP(capi.ResidentHandle):
     """Resident ALIKED on one GPU.  cfg keys follow ALIKED._default_conf (ALN:562-567)."""
 
+    _destroy = "dim_aliked_destroy"
     default_config = {"model_name": "aliked-n16rot", "max_num_keypoints": 4000, "detection_threshold": 0.2, "nms_radius": 2}
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: Optional[dict] = None, max_batch: int = 1, max_hw=(1024, 1024),
                  capacity: Optional[int] = None, device="cuda", lib=None):
         self.cfg = {**self.default_config, **(cfg or {})}
-        self.on_saturation = self.cfg.pop("on_saturation", "fallback")
-        self.arithmetic = self.cfg.pop("arithmetic", None)   # None: the process default; "fp16x3" | "fp32": this handle only
-        self.lib = lib if lib is not None else capi.load()
-        self.device = torch.device(device)
-        if lib is None and self.device.type != "cuda":
-            raise capi.DimHipError("AlikedHIP needs a HIP device; there is no CPU fallback")
-        keep = []
-
-        def host(name):
-            t = state_dict[name].detach().float().contiguous().cpu()
-            keep.append(t)
-            return t.data_ptr()
-
+        self._open(device, lib, self.cfg.pop("on_saturation", "fallback"), self.cfg.pop("arithmetic", None))
         w = _AlWeights()
         for f, k in _W_FIELDS + _TAIL:
-            setattr(w, f, host(k))
+            setattr(w, f, self._host(state_dict[k]))
         for i, b in enumerate(_BN):
-            w.bn_weight[i] = host(b + ".weight")
-            w.bn_bias[i] = host(b + ".bias")
+            w.bn_weight[i] = self._host(state_dict[b + ".weight"])
+            w.bn_bias[i] = self._host(state_dict[b + ".bias"])
         geo = ALIKED_CFGS[self.cfg["model_name"]]
         self.dim = int(geo[4])     # descriptor length: 128, or 64 for aliked-t16
         mk = int(self.cfg["max_num_keypoints"])
         self.capacity = int(capacity if capacity is not None else (mk if mk > 0 else N_LIMIT_MAX))
         c = _AlConfig(*geo, mk, float(self.cfg["detection_threshold"]), int(self.cfg["nms_radius"]))
         self.max_batch, self.max_hw = int(max_batch), (int(max_hw[0]), int(max_hw[1]))
-        self._h = ctypes.c_void_p()
-        with self._ctx():
-            capi.check(self.lib, self.lib.dim_aliked_create(ctypes.byref(w), ctypes.byref(c), self.max_batch, self.max_hw[0], self.max_hw[1],
-                                                            self.capacity, ctypes.byref(self._h)))
-        if self.arithmetic is not None:
-            capi.set_handle_arithmetic(self.lib, self._h, self.arithmetic)
-        del keep
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            self.lib.dim_aliked_destroy(h)
-            self._h = None
-
-    def _stream(self):
-        if self.device.type == "cuda":
-            return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        return None
-
-    def _ctx(self):
-        """The library launches on the CURRENT HIP device: make it the handle's."""
-        import contextlib
-        return torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext()
+        self._create(self.lib.dim_aliked_create, ctypes.byref(w), ctypes.byref(c), self.max_batch, self.max_hw[0], self.max_hw[1], self.capacity)
 
     @torch.no_grad()
     def extract_batch(self, images: torch.Tensor, out=None):
@@ -131,8 +98,7 @@ class AlikedHIP:
         """extract_batch under the fp16x3 range guard (capi.run_guarded): the full- and half-resolution convolutions and the GEMMs
         run as fp16 splits on the matrix cores (aliked_x3.hip, gemm_x6.hip), exact for |activation| <= 4094; a call that
         leaves that range is repeated on the fp32 paths.  Synchronises."""
-        with self._ctx():
-            return capi.run_guarded(self.lib, self._stream(), lambda: self.extract_batch(images), "ALIKED", self.on_saturation, logger, handle=self._h, arithmetic=self.arithmetic)
+        return self.guarded(lambda: self.extract_batch(images), "ALIKED", logger)
 
     @torch.no_grad()
     def __call__(self, image: torch.Tensor) -> dict:
@@ -144,11 +110,9 @@ class AlikedHIP:
         return {"keypoints": kp[0, :k], "scores": sc[0, :k], "descriptors": de[0, :k].t()}
 
     def debug_taps(self, batch: int = 1) -> dict:
-        from .superpoint_hip import _copy_from
-
         p1, p2 = ctypes.c_void_p(), ctypes.c_void_p()
         v = [ctypes.c_int() for _ in range(4)]
         capi.check(self.lib, self.lib.dim_aliked_debug_buffers(self._h, ctypes.byref(p1), ctypes.byref(p2), *[ctypes.byref(x) for x in v]))
         hp, wp, pt, pl = [x.value for x in v]
-        return {"x1234": _copy_from(self.lib, p1.value, (batch, hp, wp, self.dim), self.device), "pad": (pt, pl), "hp_wp": (hp, wp),
+        return {"x1234": capi.copy_from_device(self.lib, p1.value, (batch, hp, wp, self.dim), self.device), "pad": (pt, pl), "hp_wp": (hp, wp),
                 "score_ptr": p2.value}

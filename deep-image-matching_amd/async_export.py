@@ -147,7 +147,7 @@ class AsyncExporter:
 
     # ---- producer side (GPU thread) --------------------------------------------------------------------------------
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if self.device.type == "cuda" else None
+        return capi.stream_ptr(self.device)
 
     def _check(self):
         if self._err is not None:
@@ -410,7 +410,6 @@ class EndToEndRunner:
         n_img, H, W = images.shape
         cap, B, PB = self.ext.capacity, self.ext.max_batch, self.mat.max_pairs
         sync = (lambda: torch.cuda.synchronize(dev)) if dev.type == "cuda" else (lambda: None)
-        stream = (lambda: ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)) if dev.type == "cuda" else (lambda: None)
         reruns = [0]
 
         class _Count:
@@ -424,8 +423,7 @@ class EndToEndRunner:
         for s in range(0, n_img, B):
             e = min(n_img, s + B)
             chunk = images[s:e].contiguous()
-            k_, s_, d_, n_ = capi.run_guarded(lib, stream(), lambda: self.ext.extract_batch(chunk), "EndToEndRunner.extract", self.policy, _Count(),
-                                                  handle=self.ext._h, arithmetic=getattr(self.ext, "arithmetic", None))
+            k_, s_, d_, n_ = self.ext.guarded(lambda: self.ext.extract_batch(chunk), "EndToEndRunner.extract", _Count(), self.policy)
             kp[s:e], sc[s:e], de[s:e], n[s:e] = k_, s_, d_, n_
             if self.exp is not None:
                 self.exp.put_features(names[s:e], kp[s:e], sc[s:e], de[s:e], n[s:e], [(H, W)] * (e - s))
@@ -440,8 +438,7 @@ class EndToEndRunner:
         vstream = torch.cuda.Stream(device=dev) if (dev.type == "cuda" and self.ver is not None and self.overlap_verification) else None
         for s in range(0, pairs.shape[0], PB):
             pp = pairs_dev[s:s + PB].contiguous()
-            o = capi.run_guarded(lib, stream(), lambda: self.mat.match_batch(kp, de, n, size, pair_idx=pp), "EndToEndRunner.match", self.policy, _Count(),
-                                 handle=self.mat._h, arithmetic=getattr(self.mat, "arithmetic", None))
+            o = self.mat.guarded(lambda: self.mat.match_batch(kp, de, n, size, pair_idx=pp), "EndToEndRunner.match", _Count(), self.policy)
             if vstream is not None:
                 vstream.wait_stream(torch.cuda.current_stream(dev))
                 for t_ in (o["matches"], o["n_matches"], pp):

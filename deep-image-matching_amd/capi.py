@@ -4,8 +4,12 @@ There is deliberately no CPU fallback: if the gfx950 library cannot be loaded
 or no GPU is visible, loading fails with an exception."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import math
 from pathlib import Path
+
+import torch
 
 _LIB = None
 _INSTALLED_DEVICE = None
@@ -88,6 +92,33 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def stream_ptr(device):
+    """The ``void* stream`` argument of the C ABI: the CURRENT torch stream of ``device``, resolved at every call (None, the null
+    stream, off the GPU: the test emulator)."""
+    device = torch.device(device)
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream) if device.type == "cuda" else None
+
+
+def device_ctx(device):
+    """The library launches on the CURRENT HIP device: a context that makes it ``device``."""
+    device = torch.device(device)
+    return torch.cuda.device(device) if device.type == "cuda" else contextlib.nullcontext()
+
+
+def copy_from_device(lib, addr: int, shape, device) -> torch.Tensor:
+    """Copy a raw fp32 device buffer into a CPU tensor (hipMemcpy through torch)."""
+    n = math.prod(shape)
+    if device.type == "cuda":
+        torch.cuda.synchronize(device)
+        out = torch.empty(n, dtype=torch.float32, device=device)
+        rc = ctypes.CDLL("libamdhip64.so").hipMemcpy(ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(addr), ctypes.c_size_t(n * 4), 3)
+        if rc != 0:
+            raise DimHipError(f"hipMemcpy failed: {rc}")
+        return out.cpu().reshape(shape)
+    buf = (ctypes.c_float * n).from_address(addr)
+    return torch.frombuffer(buf, dtype=torch.float32).clone().reshape(shape)
+
+
 # ---- arithmetic selection and the fp16x3 range guard ------------------------------------------------------
 ARITHMETIC = {"fp16x3": 2, "bf16x6": 1, "fp32": 0}
 SAT_SITES = 16  # DIM_SAT_SITES
@@ -158,3 +189,54 @@ def run_guarded(lib, stream, fn, what: str, policy: str = "fallback", logger=Non
         return fn()
     finally:
         set_arithmetic(lib, prev)
+
+
+class ResidentHandle:
+    """Base of the four wrappers of a resident ``dim_*_create`` handle: ``lib`` / ``device`` / ``_h``, the no-fallback rule, create and
+    (idempotent) destroy, the stream / device context of a call and the fp16x3 range guard around one."""
+
+    _destroy = ""   # name of the C destroy function
+    _h = None       # null until create succeeded, None again after destroy
+
+    def _open(self, device, lib, on_saturation="fallback", arithmetic=None):
+        self.arithmetic = arithmetic        # None: the process default (set_arithmetic); "fp16x3" | "bf16x6" | "fp32": this handle only
+        self.on_saturation = on_saturation  # fp16x3 range guard policy: "fallback" (bf16x6 re-run) | "raise" | "off"
+        self.lib = lib if lib is not None else load()
+        self.device = torch.device(device)
+        if self.device.type != "cuda" and lib is None and installed_device() is None:
+            raise DimHipError(f"{type(self).__name__} needs a HIP device; there is no CPU fallback")
+        self._h = ctypes.c_void_p()
+        self._keep = []
+
+    def _host(self, t) -> int:
+        """Address of ``t`` as contiguous fp32 host memory, kept alive until ``_create`` returns."""
+        t = t.detach().float().contiguous().cpu()
+        self._keep.append(t)
+        return t.data_ptr()
+
+    def _create(self, create, *args):
+        """``create(*args, &handle)`` on the handle's device, then the handle's own arithmetic."""
+        try:
+            with self._ctx():
+                check(self.lib, create(*args, ctypes.byref(self._h)))
+        finally:
+            self._keep = []
+        if self.arithmetic is not None:
+            set_handle_arithmetic(self.lib, self._h, self.arithmetic)
+
+    def __del__(self):
+        h, self._h = self._h, None
+        if h:
+            getattr(self.lib, self._destroy)(h)
+
+    def _stream(self):
+        return stream_ptr(self.device)
+
+    def _ctx(self):
+        return device_ctx(self.device)
+
+    def guarded(self, fn, what: str, logger=None, policy=None):
+        """``fn()`` (calls on this handle, enqueued on the current stream) under the fp16x3 range guard (run_guarded): synchronises."""
+        with self._ctx():
+            return run_guarded(self.lib, self._stream(), fn, what, self.on_saturation if policy is None else policy, logger,
+                               handle=self._h, arithmetic=self.arithmetic)

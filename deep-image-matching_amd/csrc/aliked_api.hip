@@ -33,32 +33,10 @@ struct dim_aliked {
   int *cand_idx, *rowcount, *rowoff, *ncand;
   unsigned long long* topk_keys;   // launch_topk's global key table (n_limit > 4096 only)
   int last_hp, last_wp, last_h, last_w, last_batch;
-  float* dbg_x1234;  // debug tap only: materialised on request by dim_aliked_debug_buffers
-  std::vector<void*> allocs;
+  float* dbg_x1234;  // debug tap only: materialised (and resized) on request by dim_aliked_debug_buffers, not part of the base's allocations
 };
 
 namespace {
-template <typename T>
-int dev_alloc(dim_aliked* h, T** p, size_t count) {
-  void* q = nullptr;
-  hipError_t e = hipMalloc(&q, count * sizeof(T) + 256);
-  if (e != hipSuccess) {
-    dim_set_error("hipMalloc of %zu bytes failed: out of memory (%s)", count * sizeof(T), hipGetErrorString(e));
-    return -1;
-  }
-  h->allocs.push_back(q);
-  *p = (T*)q;
-  return 0;
-}
-int upload(dim_aliked* h, float** dst, const std::vector<float>& v) {
-  if (!dim_all_finite(v.data(), v.size())) { dim_set_error("non-finite value in the weights"); return -1; }
-  if (dev_alloc(h, dst, v.size()) != 0) return -1;
-  if (hipMemcpy(*dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    dim_set_error("weight upload failed");
-    return -1;
-  }
-  return 0;
-}
 // OIHW -> [tap][cin_pad][cout_pad] (zero padded)
 std::vector<float> relayout(const float* w, int co, int ci, int k, int ci_pad, int co_pad) {
   std::vector<float> o((size_t)k * k * ci_pad * co_pad, 0.0f);
@@ -68,27 +46,9 @@ std::vector<float> relayout(const float* w, int co, int ci, int k, int ci_pad, i
   return o;
 }
 // [K][N] fp32 conv operand (K = tap * cin_pad + ci) -> fp16x3 MFMA fragments + per-channel inverse scales (n_pad = 32)
-int upload_x3(dim_aliked* h, SplitWeights* dst, const std::vector<float>& w_kn, int K, int N) {
-  if (!dim_all_finite(w_kn.data(), w_kn.size())) { dim_set_error("non-finite value in the weights"); return -1; }
-  std::vector<unsigned short> host(gemm_split_weight_elems(K, 32, 2));
-  split_weights(w_kn.data(), K, N, 32, 2, host.data(), dst);
-  unsigned short* d = nullptr;
-  if (dev_alloc(h, &d, host.size()) != 0) return -1;
-  if (hipMemcpy(d, host.data(), host.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { dim_set_error("weight upload failed"); return -1; }
-  dst->dev = d; dst->mode = 2; dst->n_pad = 32;
-  return 0;
-}
+int upload_x3(DimHandleBase* hb, SplitWeights* dst, const std::vector<float>& w_kn, int K, int N) { return dim_upload_gemm_split(hb, dst, w_kn.data(), K, N, 32, 2); }
 // [K][N] fp32 GEMM operand -> fp16x3 planes in gemm_x6's fragment order (n_pad = multiple of 128)
-int upload_x3g(dim_aliked* h, SplitWeights* dst, const float* w_kn, int K, int N) {
-  const int n_pad = (N + 127) / 128 * 128;
-  std::vector<unsigned short> host(gemm_split_weight_elems(K, n_pad, 2));
-  split_weights(w_kn, K, N, n_pad, 2, host.data(), dst);
-  unsigned short* d = nullptr;
-  if (dev_alloc(h, &d, host.size()) != 0) return -1;
-  if (hipMemcpy(d, host.data(), host.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { dim_set_error("weight upload failed"); return -1; }
-  dst->dev = d; dst->mode = 2; dst->n_pad = n_pad;
-  return 0;
-}
+int upload_x3g(DimHandleBase* hb, SplitWeights* dst, const float* w_kn, int K, int N) { return dim_upload_gemm_split(hb, dst, w_kn, K, N, (N + 127) / 128 * 128, 2); }
 std::vector<float> padvec(const float* b, int n, int n_pad) {
   std::vector<float> v(n_pad, 0.0f);
   for (int i = 0; i < n; ++i) v[i] = b[i];
@@ -100,7 +60,7 @@ extern "C" {
 
 void dim_aliked_destroy(dim_aliked* h) {
   if (!h) return;
-  for (void* p : h->allocs) hipFree(p);
+  dim_handle_release(&h->base);
   if (h->dbg_x1234) hipFree(h->dbg_x1234);
   delete h;
 }
@@ -122,104 +82,103 @@ int dim_aliked_create(const dim_aliked_weights* w, const dim_aliked_config* cfg,
   DIM_REQUIRE(cfg->nms_radius >= 1 && cfg->nms_radius <= 6, "dim_aliked_create: nms_radius %d", cfg->nms_radius);
   DIM_REQUIRE(capacity > 0 && capacity <= 32768 && cfg->max_num_keypoints <= capacity, "dim_aliked_create: capacity %d (<= 32768) must cover max_num_keypoints %d", capacity, cfg->max_num_keypoints);
   DIM_REQUIRE(max_batch > 0 && max_batch <= 64 && max_h >= 16 && max_w >= 16, "dim_aliked_create: bad sizes");
-  dim_aliked* h = new dim_aliked();
+  std::unique_ptr<dim_aliked, void (*)(dim_aliked*)> guard(new dim_aliked(), dim_aliked_destroy);
+  dim_aliked* const h = guard.get();
+  DimHandleBase* const hb = &h->base;
   h->cfg = *cfg;
   h->max_batch = max_batch; h->max_h = max_h; h->max_w = max_w; h->capacity = capacity;
-#define AL_TRY(x) do { if ((x) != 0) { dim_aliked_destroy(h); return -1; } } while (0)
   // [tap][ci][co] operand of a deformable convolution's GEMM with the rows padded to the K granule (al_deform_krow: aliked-t16's 144 -> 160)
   auto deform_w = [&](const float* w_, int co, int ci) {
     std::vector<float> v = relayout(w_, co, ci, 3, ci, co);
     v.resize((size_t)al_deform_krow(ci) * co, 0.0f);
     return v;
   };
-  AL_TRY(upload(h, &h->b1c1, relayout(w->block1_conv1, c1, 3, 3, 4, c1)));
-  AL_TRY(upload(h, &h->b1c2, relayout(w->block1_conv2, c1, c1, 3, c1, c1)));
-  AL_TRY(upload(h, &h->b2c1, relayout(w->block2_conv1, c2, c1, 3, c1, c2)));
-  AL_TRY(upload(h, &h->b2c2, relayout(w->block2_conv2, c2, c2, 3, c2, c2)));
-  AL_TRY(upload(h, &h->b2ds_w, relayout(w->block2_ds_w, c2, c1, 1, c1, c2))); AL_TRY(upload(h, &h->b2ds_b, padvec(w->block2_ds_b, c2, c2)));
-  AL_TRY(upload(h, &h->b3o1_w, relayout(w->block3_off1_w, 18, c2, 3, c2, 20))); AL_TRY(upload(h, &h->b3o1_b, padvec(w->block3_off1_b, 18, 20)));
-  AL_TRY(upload(h, &h->b3r1, deform_w(w->block3_reg1, c3, c2)));
-  AL_TRY(upload(h, &h->b3o2_w, relayout(w->block3_off2_w, 18, c3, 3, c3, 20))); AL_TRY(upload(h, &h->b3o2_b, padvec(w->block3_off2_b, 18, 20)));
-  AL_TRY(upload(h, &h->b3r2, deform_w(w->block3_reg2, c3, c3)));
-  AL_TRY(upload(h, &h->b3ds_w, relayout(w->block3_ds_w, c3, c2, 1, c2, c3))); AL_TRY(upload(h, &h->b3ds_b, padvec(w->block3_ds_b, c3, c3)));
-  AL_TRY(upload(h, &h->b4o1_w, relayout(w->block4_off1_w, 18, c3, 3, c3, 20))); AL_TRY(upload(h, &h->b4o1_b, padvec(w->block4_off1_b, 18, 20)));
-  AL_TRY(upload(h, &h->b4r1, deform_w(w->block4_reg1, c4, c3)));
-  AL_TRY(upload(h, &h->b4o2_w, relayout(w->block4_off2_w, 18, c4, 3, c4, 20))); AL_TRY(upload(h, &h->b4o2_b, padvec(w->block4_off2_b, 18, 20)));
-  AL_TRY(upload(h, &h->b4r2, deform_w(w->block4_reg2, c4, c4)));
-  AL_TRY(upload(h, &h->b4ds_w, relayout(w->block4_ds_w, c4, c3, 1, c3, c4))); AL_TRY(upload(h, &h->b4ds_b, padvec(w->block4_ds_b, c4, c4)));
+  DIM_TRY(dim_upload_f32(hb, &h->b1c1, relayout(w->block1_conv1, c1, 3, 3, 4, c1)));
+  DIM_TRY(dim_upload_f32(hb, &h->b1c2, relayout(w->block1_conv2, c1, c1, 3, c1, c1)));
+  DIM_TRY(dim_upload_f32(hb, &h->b2c1, relayout(w->block2_conv1, c2, c1, 3, c1, c2)));
+  DIM_TRY(dim_upload_f32(hb, &h->b2c2, relayout(w->block2_conv2, c2, c2, 3, c2, c2)));
+  DIM_TRY(dim_upload_f32(hb, &h->b2ds_w, relayout(w->block2_ds_w, c2, c1, 1, c1, c2))); DIM_TRY(dim_upload_f32(hb, &h->b2ds_b, padvec(w->block2_ds_b, c2, c2)));
+  DIM_TRY(dim_upload_f32(hb, &h->b3o1_w, relayout(w->block3_off1_w, 18, c2, 3, c2, 20))); DIM_TRY(dim_upload_f32(hb, &h->b3o1_b, padvec(w->block3_off1_b, 18, 20)));
+  DIM_TRY(dim_upload_f32(hb, &h->b3r1, deform_w(w->block3_reg1, c3, c2)));
+  DIM_TRY(dim_upload_f32(hb, &h->b3o2_w, relayout(w->block3_off2_w, 18, c3, 3, c3, 20))); DIM_TRY(dim_upload_f32(hb, &h->b3o2_b, padvec(w->block3_off2_b, 18, 20)));
+  DIM_TRY(dim_upload_f32(hb, &h->b3r2, deform_w(w->block3_reg2, c3, c3)));
+  DIM_TRY(dim_upload_f32(hb, &h->b3ds_w, relayout(w->block3_ds_w, c3, c2, 1, c2, c3))); DIM_TRY(dim_upload_f32(hb, &h->b3ds_b, padvec(w->block3_ds_b, c3, c3)));
+  DIM_TRY(dim_upload_f32(hb, &h->b4o1_w, relayout(w->block4_off1_w, 18, c3, 3, c3, 20))); DIM_TRY(dim_upload_f32(hb, &h->b4o1_b, padvec(w->block4_off1_b, 18, 20)));
+  DIM_TRY(dim_upload_f32(hb, &h->b4r1, deform_w(w->block4_reg1, c4, c3)));
+  DIM_TRY(dim_upload_f32(hb, &h->b4o2_w, relayout(w->block4_off2_w, 18, c4, 3, c4, 20))); DIM_TRY(dim_upload_f32(hb, &h->b4o2_b, padvec(w->block4_off2_b, 18, 20)));
+  DIM_TRY(dim_upload_f32(hb, &h->b4r2, deform_w(w->block4_reg2, c4, c4)));
+  DIM_TRY(dim_upload_f32(hb, &h->b4ds_w, relayout(w->block4_ds_w, c4, c3, 1, c3, c4))); DIM_TRY(dim_upload_f32(hb, &h->b4ds_b, padvec(w->block4_ds_b, c4, c4)));
   if (normal) {   // the matrix-core forms of the full- / half-resolution convolutions and of the aggregation exist for the 16 / 32-channel geometry
-    AL_TRY(upload_x3(h, &h->x_b1c1, relayout(w->block1_conv1, 16, 3, 3, 16, 16), 9 * 16, 16));
-    AL_TRY(upload_x3(h, &h->x_b1c2, relayout(w->block1_conv2, 16, 16, 3, 16, 16), 9 * 16, 16));
-    AL_TRY(upload_x3(h, &h->x_b2c1, relayout(w->block2_conv1, 32, 16, 3, 16, 32), 9 * 16, 32));
-    AL_TRY(upload_x3(h, &h->x_b2c2, relayout(w->block2_conv2, 32, 32, 3, 32, 32), 9 * 32, 32));
-    AL_TRY(upload_x3(h, &h->x_b2ds, relayout(w->block2_ds_w, 32, 16, 1, 16, 32), 16, 32));
+    DIM_TRY(upload_x3(hb, &h->x_b1c1, relayout(w->block1_conv1, 16, 3, 3, 16, 16), 9 * 16, 16));
+    DIM_TRY(upload_x3(hb, &h->x_b1c2, relayout(w->block1_conv2, 16, 16, 3, 16, 16), 9 * 16, 16));
+    DIM_TRY(upload_x3(hb, &h->x_b2c1, relayout(w->block2_conv1, 32, 16, 3, 16, 32), 9 * 16, 32));
+    DIM_TRY(upload_x3(hb, &h->x_b2c2, relayout(w->block2_conv2, 32, 32, 3, 32, 32), 9 * 32, 32));
+    DIM_TRY(upload_x3(hb, &h->x_b2ds, relayout(w->block2_ds_w, 32, 16, 1, 16, 32), 16, 32));
   }
   {  // the same operands the fp32 GEMMs use ([K][N] row-major), split for the matrix cores
     auto kn = [&](const float* w_, int co, int ci, int k) { return relayout(w_, co, ci, k, ci, co); };
-    AL_TRY(upload_x3g(h, &h->g_b3r1, deform_w(w->block3_reg1, c3, c2).data(), al_deform_krow(c2), c3)); AL_TRY(upload_x3g(h, &h->g_b3r2, deform_w(w->block3_reg2, c3, c3).data(), al_deform_krow(c3), c3));
-    AL_TRY(upload_x3g(h, &h->g_b4r1, deform_w(w->block4_reg1, c4, c3).data(), al_deform_krow(c3), c4)); AL_TRY(upload_x3g(h, &h->g_b4r2, deform_w(w->block4_reg2, c4, c4).data(), al_deform_krow(c4), c4));
-    AL_TRY(upload_x3g(h, &h->g_b4ds, kn(w->block4_ds_w, c4, c3, 1).data(), c3, c4));
+    DIM_TRY(upload_x3g(hb, &h->g_b3r1, deform_w(w->block3_reg1, c3, c2).data(), al_deform_krow(c2), c3)); DIM_TRY(upload_x3g(hb, &h->g_b3r2, deform_w(w->block3_reg2, c3, c3).data(), al_deform_krow(c3), c3));
+    DIM_TRY(upload_x3g(hb, &h->g_b4r1, deform_w(w->block4_reg1, c4, c3).data(), al_deform_krow(c3), c4)); DIM_TRY(upload_x3g(hb, &h->g_b4r2, deform_w(w->block4_reg2, c4, c4).data(), al_deform_krow(c4), c4));
+    DIM_TRY(upload_x3g(hb, &h->g_b4ds, kn(w->block4_ds_w, c4, c3, 1).data(), c3, c4));
     if (normal) {
-      AL_TRY(upload_x3g(h, &h->g_b3ds, kn(w->block3_ds_w, 64, 32, 1).data(), 32, 64));
-      AL_TRY(upload_x3g(h, &h->g_hc2, kn(w->conv2, 32, 32, 1).data(), 32, 32)); AL_TRY(upload_x3g(h, &h->g_hc3, kn(w->conv3, 32, 64, 1).data(), 64, 32));
-      AL_TRY(upload_x3g(h, &h->g_hc4, kn(w->conv4, 32, 128, 1).data(), 128, 32));
+      DIM_TRY(upload_x3g(hb, &h->g_b3ds, kn(w->block3_ds_w, 64, 32, 1).data(), 32, 64));
+      DIM_TRY(upload_x3g(hb, &h->g_hc2, kn(w->conv2, 32, 32, 1).data(), 32, 32)); DIM_TRY(upload_x3g(hb, &h->g_hc3, kn(w->conv3, 32, 64, 1).data(), 64, 32));
+      DIM_TRY(upload_x3g(hb, &h->g_hc4, kn(w->conv4, 32, 128, 1).data(), 128, 32));
     }
-    AL_TRY(upload_x3g(h, &h->g_sf, kn(w->desc_sf, dim, dim, 1).data(), dim, dim));
-    AL_TRY(upload_x3g(h, &h->g_agg, w->desc_agg, M * dim, dim));
+    DIM_TRY(upload_x3g(hb, &h->g_sf, kn(w->desc_sf, dim, dim, 1).data(), dim, dim));
+    DIM_TRY(upload_x3g(hb, &h->g_agg, w->desc_agg, M * dim, dim));
     std::vector<float> o0((size_t)dim * 9 * M2);
     for (int co = 0; co < M2; ++co)
       for (int k = 0; k < dim * 9; ++k) o0[(size_t)k * M2 + co] = w->desc_off0_w[(size_t)co * dim * 9 + k];
-    AL_TRY(upload_x3g(h, &h->g_o0, o0.data(), dim * 9, M2));
+    DIM_TRY(upload_x3g(hb, &h->g_o0, o0.data(), dim * 9, M2));
   }
   if (normal) {
     const std::vector<float> w1 = relayout(w->conv1, 32, 16, 1, 16, 32), ws0 = relayout(w->score0, 8, 128, 1, 128, 8);
     std::vector<unsigned short> frag(al_assemble_x3_frag_halves());
     std::vector<float> inv1(32);
     al_assemble_x3_prepare(w1.data(), ws0.data(), frag.data(), inv1.data(), &h->asm_inv0);
-    AL_TRY(dev_alloc(h, &h->asm_frag, frag.size()));
-    AL_TRY(upload(h, &h->asm_inv1, inv1));
-    if (hipMemcpy(h->asm_frag, frag.data(), frag.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { dim_set_error("weight upload failed"); dim_aliked_destroy(h); return -1; }
+    DIM_TRY(dim_upload(hb, &h->asm_frag, frag.data(), frag.size()));
+    DIM_TRY(dim_upload_f32(hb, &h->asm_inv1, inv1));
   }
   const int bnc[8] = {c1, c1, c2, c2, c3, c3, c4, c4};
   for (int i = 0; i < 8; ++i) {
-    AL_TRY(upload(h, &h->bn_g[i], padvec(w->bn_weight[i], bnc[i], bnc[i])));
-    AL_TRY(upload(h, &h->bn_b[i], padvec(w->bn_bias[i], bnc[i], bnc[i])));
+    DIM_TRY(dim_upload_f32(hb, &h->bn_g[i], padvec(w->bn_weight[i], bnc[i], bnc[i])));
+    DIM_TRY(dim_upload_f32(hb, &h->bn_b[i], padvec(w->bn_bias[i], bnc[i], bnc[i])));
   }
-  AL_TRY(upload(h, &h->hc1, relayout(w->conv1, G, c1, 1, c1, G))); AL_TRY(upload(h, &h->hc2, relayout(w->conv2, G, c2, 1, c2, G)));
-  AL_TRY(upload(h, &h->hc3, relayout(w->conv3, G, c3, 1, c3, G))); AL_TRY(upload(h, &h->hc4, relayout(w->conv4, G, c4, 1, c4, G)));
-  AL_TRY(upload(h, &h->sh0, relayout(w->score0, 8, dim, 1, dim, 8))); AL_TRY(upload(h, &h->sh2, relayout(w->score2, 4, 8, 3, 8, 4)));
-  AL_TRY(upload(h, &h->sh4, relayout(w->score4, 4, 4, 3, 4, 4))); AL_TRY(upload(h, &h->sh6, relayout(w->score6, 1, 4, 3, 4, 4)));
+  DIM_TRY(dim_upload_f32(hb, &h->hc1, relayout(w->conv1, G, c1, 1, c1, G))); DIM_TRY(dim_upload_f32(hb, &h->hc2, relayout(w->conv2, G, c2, 1, c2, G)));
+  DIM_TRY(dim_upload_f32(hb, &h->hc3, relayout(w->conv3, G, c3, 1, c3, G))); DIM_TRY(dim_upload_f32(hb, &h->hc4, relayout(w->conv4, G, c4, 1, c4, G)));
+  DIM_TRY(dim_upload_f32(hb, &h->sh0, relayout(w->score0, 8, dim, 1, dim, 8))); DIM_TRY(dim_upload_f32(hb, &h->sh2, relayout(w->score2, 4, 8, 3, 8, 4)));
+  DIM_TRY(dim_upload_f32(hb, &h->sh4, relayout(w->score4, 4, 4, 3, 4, 4))); DIM_TRY(dim_upload_f32(hb, &h->sh6, relayout(w->score6, 1, 4, 3, 4, 4)));
   {  // SDDH: offset_conv.0 (2M,dim,3,3) -> GEMM operand [ci*9+tap][2M]; offset_conv.2 (2M,2M,1,1) -> [in][out]
     std::vector<float> o0((size_t)dim * 9 * M2);
     for (int co = 0; co < M2; ++co)
       for (int k = 0; k < dim * 9; ++k) o0[(size_t)k * M2 + co] = w->desc_off0_w[(size_t)co * dim * 9 + k];
-    AL_TRY(upload(h, &h->dh_o0_w, o0)); AL_TRY(upload(h, &h->dh_o0_b, padvec(w->desc_off0_b, M2, M2)));
-    AL_TRY(upload(h, &h->dh_o2_w, relayout(w->desc_off2_w, M2, M2, 1, M2, M2))); AL_TRY(upload(h, &h->dh_o2_b, padvec(w->desc_off2_b, M2, M2)));
-    AL_TRY(upload(h, &h->dh_sf, relayout(w->desc_sf, dim, dim, 1, dim, dim)));
-    AL_TRY(upload(h, &h->dh_agg, padvec(w->desc_agg, M * dim * dim, M * dim * dim)));  // [p][c][d] == GEMM operand [p*dim+c][d]
+    DIM_TRY(dim_upload_f32(hb, &h->dh_o0_w, o0)); DIM_TRY(dim_upload_f32(hb, &h->dh_o0_b, padvec(w->desc_off0_b, M2, M2)));
+    DIM_TRY(dim_upload_f32(hb, &h->dh_o2_w, relayout(w->desc_off2_w, M2, M2, 1, M2, M2))); DIM_TRY(dim_upload_f32(hb, &h->dh_o2_b, padvec(w->desc_off2_b, M2, M2)));
+    DIM_TRY(dim_upload_f32(hb, &h->dh_sf, relayout(w->desc_sf, dim, dim, 1, dim, dim)));
+    DIM_TRY(dim_upload_f32(hb, &h->dh_agg, padvec(w->desc_agg, M * dim * dim, M * dim * dim)));  // [p][c][d] == GEMM operand [p*dim+c][d]
   }
   const size_t B = max_batch;
   const size_t Hp = ((size_t)max_h + 31) / 32 * 32, Wp = ((size_t)max_w + 31) / 32 * 32, NP = Hp * Wp, cap = capacity;
-  AL_TRY(dev_alloc(h, &h->cols, B * NP / 64 * al_deform_krow(c3)));  // deformed im2col rows: block3 (1/8 res, K = 9 * c3) is the largest
-  AL_TRY(dev_alloc(h, &h->P, B * NP * 3)); AL_TRY(dev_alloc(h, &h->raw, B * NP * c1)); AL_TRY(dev_alloc(h, &h->act, B * NP * c1));
-  AL_TRY(dev_alloc(h, &h->x1, B * NP * c1)); AL_TRY(dev_alloc(h, &h->p2, B * NP / 4 * c1)); AL_TRY(dev_alloc(h, &h->idn, B * NP / 4 * c2));
-  AL_TRY(dev_alloc(h, &h->x2, B * NP / 4 * c2)); AL_TRY(dev_alloc(h, &h->p3, B * NP / 64 * c2)); AL_TRY(dev_alloc(h, &h->off, B * NP / 64 * 20));
-  AL_TRY(dev_alloc(h, &h->x3, B * NP / 64 * c3)); AL_TRY(dev_alloc(h, &h->p4, B * NP / 1024 * c3)); AL_TRY(dev_alloc(h, &h->x4, B * NP / 1024 * c4));
-  AL_TRY(dev_alloc(h, &h->f2, B * NP / 4 * G)); AL_TRY(dev_alloc(h, &h->f3, B * NP / 64 * G)); AL_TRY(dev_alloc(h, &h->f4, B * NP / 1024 * G));
-  AL_TRY(dev_alloc(h, &h->q2, B * NP / 4 * 8)); AL_TRY(dev_alloc(h, &h->q3, B * NP / 64 * 8)); AL_TRY(dev_alloc(h, &h->q4, B * NP / 1024 * 8));
-  AL_TRY(dev_alloc(h, &h->s8, B * NP * 8)); AL_TRY(dev_alloc(h, &h->s4a, B * NP * 4));
-  AL_TRY(dev_alloc(h, &h->s4b, B * NP * 4)); AL_TRY(dev_alloc(h, &h->score, B * NP)); AL_TRY(dev_alloc(h, &h->nms, B * NP));
-  AL_TRY(dev_alloc(h, &h->cand_score, B * NP)); AL_TRY(dev_alloc(h, &h->cand_idx, B * NP)); AL_TRY(dev_alloc(h, &h->rowcount, B * Hp));
-  AL_TRY(dev_alloc(h, &h->rowoff, B * Hp)); AL_TRY(dev_alloc(h, &h->ncand, B)); AL_TRY(dev_alloc(h, &h->kpts_px, B * cap * 2));
-  AL_TRY(dev_alloc(h, &h->sc_tmp, B * cap)); AL_TRY(dev_alloc(h, &h->kpts_norm, B * cap * 2)); AL_TRY(dev_alloc(h, &h->kscore, B * cap));
-  AL_TRY(dev_alloc(h, &h->patches, B * cap * dim * 9)); AL_TRY(dev_alloc(h, &h->hidden, B * cap * M2)); AL_TRY(dev_alloc(h, &h->feats, B * cap * M * dim));
-  AL_TRY(dev_alloc(h, &h->feats2, B * cap * M * dim)); AL_TRY(dev_alloc(h, &h->bn_alpha, 2 * B * 128)); AL_TRY(dev_alloc(h, &h->bn_beta, 2 * B * 128));   // two slots: a conv's input and output BatchNorm
-  AL_TRY(dev_alloc(h, &h->mean, B)); AL_TRY(dev_alloc(h, &h->thr_eff, B)); AL_TRY(dev_alloc(h, &h->partial, B * 256 * 128 * 2));
-  AL_TRY(dev_alloc(h, &h->tile_partial, al_convx3_partial_doubles((int)B, (int)Hp, (int)Wp)));
+  DIM_TRY(dim_dev_alloc(hb, &h->cols, B * NP / 64 * al_deform_krow(c3)));  // deformed im2col rows: block3 (1/8 res, K = 9 * c3) is the largest
+  DIM_TRY(dim_dev_alloc(hb, &h->P, B * NP * 3)); DIM_TRY(dim_dev_alloc(hb, &h->raw, B * NP * c1)); DIM_TRY(dim_dev_alloc(hb, &h->act, B * NP * c1));
+  DIM_TRY(dim_dev_alloc(hb, &h->x1, B * NP * c1)); DIM_TRY(dim_dev_alloc(hb, &h->p2, B * NP / 4 * c1)); DIM_TRY(dim_dev_alloc(hb, &h->idn, B * NP / 4 * c2));
+  DIM_TRY(dim_dev_alloc(hb, &h->x2, B * NP / 4 * c2)); DIM_TRY(dim_dev_alloc(hb, &h->p3, B * NP / 64 * c2)); DIM_TRY(dim_dev_alloc(hb, &h->off, B * NP / 64 * 20));
+  DIM_TRY(dim_dev_alloc(hb, &h->x3, B * NP / 64 * c3)); DIM_TRY(dim_dev_alloc(hb, &h->p4, B * NP / 1024 * c3)); DIM_TRY(dim_dev_alloc(hb, &h->x4, B * NP / 1024 * c4));
+  DIM_TRY(dim_dev_alloc(hb, &h->f2, B * NP / 4 * G)); DIM_TRY(dim_dev_alloc(hb, &h->f3, B * NP / 64 * G)); DIM_TRY(dim_dev_alloc(hb, &h->f4, B * NP / 1024 * G));
+  DIM_TRY(dim_dev_alloc(hb, &h->q2, B * NP / 4 * 8)); DIM_TRY(dim_dev_alloc(hb, &h->q3, B * NP / 64 * 8)); DIM_TRY(dim_dev_alloc(hb, &h->q4, B * NP / 1024 * 8));
+  DIM_TRY(dim_dev_alloc(hb, &h->s8, B * NP * 8)); DIM_TRY(dim_dev_alloc(hb, &h->s4a, B * NP * 4));
+  DIM_TRY(dim_dev_alloc(hb, &h->s4b, B * NP * 4)); DIM_TRY(dim_dev_alloc(hb, &h->score, B * NP)); DIM_TRY(dim_dev_alloc(hb, &h->nms, B * NP));
+  DIM_TRY(dim_dev_alloc(hb, &h->cand_score, B * NP)); DIM_TRY(dim_dev_alloc(hb, &h->cand_idx, B * NP)); DIM_TRY(dim_dev_alloc(hb, &h->rowcount, B * Hp));
+  DIM_TRY(dim_dev_alloc(hb, &h->rowoff, B * Hp)); DIM_TRY(dim_dev_alloc(hb, &h->ncand, B)); DIM_TRY(dim_dev_alloc(hb, &h->kpts_px, B * cap * 2));
+  DIM_TRY(dim_dev_alloc(hb, &h->sc_tmp, B * cap)); DIM_TRY(dim_dev_alloc(hb, &h->kpts_norm, B * cap * 2)); DIM_TRY(dim_dev_alloc(hb, &h->kscore, B * cap));
+  DIM_TRY(dim_dev_alloc(hb, &h->patches, B * cap * dim * 9)); DIM_TRY(dim_dev_alloc(hb, &h->hidden, B * cap * M2)); DIM_TRY(dim_dev_alloc(hb, &h->feats, B * cap * M * dim));
+  DIM_TRY(dim_dev_alloc(hb, &h->feats2, B * cap * M * dim)); DIM_TRY(dim_dev_alloc(hb, &h->bn_alpha, 2 * B * 128)); DIM_TRY(dim_dev_alloc(hb, &h->bn_beta, 2 * B * 128));   // two slots: a conv's input and output BatchNorm
+  DIM_TRY(dim_dev_alloc(hb, &h->mean, B)); DIM_TRY(dim_dev_alloc(hb, &h->thr_eff, B)); DIM_TRY(dim_dev_alloc(hb, &h->partial, B * 256 * 128 * 2));
+  DIM_TRY(dim_dev_alloc(hb, &h->tile_partial, al_convx3_partial_doubles((int)B, (int)Hp, (int)Wp)));
   h->topk_keys = nullptr;
-  if (topk_scratch_keys(max_batch, capacity)) AL_TRY(dev_alloc(h, &h->topk_keys, topk_scratch_keys(max_batch, capacity)));
-#undef AL_TRY
-  *out = h;
+  if (topk_scratch_keys(max_batch, capacity)) DIM_TRY(dim_dev_alloc(hb, &h->topk_keys, topk_scratch_keys(max_batch, capacity)));
+  *out = guard.release();
   return 0;
 }
 

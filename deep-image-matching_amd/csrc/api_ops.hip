@@ -55,6 +55,49 @@ void dim_sat_host_bump(int site) {
 static thread_local const DimTune* g_tune_scope = nullptr;
 void dim_tune_scope_set(const DimTune* t) { g_tune_scope = t; }
 const DimTune* dim_tune_scope_get() { return g_tune_scope; }
+// the device memory of a handle (DimHandleBase in dim_common.h)
+int dim_dev_alloc_bytes(DimHandleBase* b, void** p, size_t bytes) {
+  void* q = nullptr;
+  const hipError_t e = hipMalloc(&q, bytes + DIM_ALLOC_SLACK);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    dim_set_error("hipMalloc of %zu bytes failed: out of memory (%s)", bytes, hipGetErrorString(e));
+    return -1;
+  }
+  b->allocs.push_back(q);
+  b->bytes += bytes;
+  *p = q;
+  return 0;
+}
+int dim_upload_bytes(DimHandleBase* b, void** dst, const void* src, size_t bytes) {
+  if (dim_dev_alloc_bytes(b, dst, bytes) != 0) return -1;
+  if (hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    dim_set_error("weight upload failed");
+    return -1;
+  }
+  return 0;
+}
+int dim_upload_f32(DimHandleBase* b, float** dst, const float* src, size_t count) {
+  if (!dim_all_finite(src, count)) { dim_set_error("non-finite value in the weights"); return -1; }
+  return dim_upload(b, dst, src, count);
+}
+int dim_upload_split(DimHandleBase* b, SplitWeights* sw, const std::vector<unsigned short>& host, int mode, int n_pad) {
+  unsigned short* d = nullptr;
+  if (dim_upload(b, &d, host.data(), host.size()) != 0) return -1;
+  sw->dev = d; sw->mode = mode; sw->n_pad = n_pad;
+  return 0;
+}
+int dim_upload_gemm_split(DimHandleBase* b, SplitWeights* sw, const float* w_kn, int K, int N, int n_pad, int mode, int kperm) {
+  if (!dim_all_finite(w_kn, (size_t)K * N)) { dim_set_error("non-finite value in the weights"); return -1; }
+  std::vector<unsigned short> host(gemm_split_weight_elems(K, n_pad, mode));
+  split_weights(w_kn, K, N, n_pad, mode, host.data(), sw, kperm);
+  return dim_upload_split(b, sw, host, mode, n_pad);
+}
+void dim_handle_release(DimHandleBase* b) {
+  for (void* p : b->allocs) hipFree(p);
+  b->allocs.clear();
+  b->bytes = 0;
+}
 static inline int tuned(int key, int process_default) {
   const DimTune* t = g_tune_scope;
   return (t && t->v[key] >= 0) ? t->v[key] : process_default;

@@ -5,6 +5,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <memory>
+#include <vector>
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -323,9 +326,12 @@ void dim_sat_host_bump(int site);  // a range violation established on the host 
     }                                     \
   } while (0)
 
-// ---- per-handle overrides of the dim_tune_set choices (include/dim_hip.h: dim_handle_tune_set) ----
-// Every extractor / matcher handle starts with a DimHandleBase; the C-ABI entry points open a DimTuneScope on it, and the accessors
-// (dim_precision_mode(), dim_fuse_conv1a(), ...) return the handle's override while the scope is open on this thread, else the process default.
+// ---- the base of every extractor / matcher handle -----------------------------------------------
+// Every handle starts with a DimHandleBase.  It carries (a) the per-handle overrides of the dim_tune_set choices (include/dim_hip.h:
+// dim_handle_tune_set): the C-ABI entry points open a DimTuneScope on it, and the accessors (dim_precision_mode(), dim_fuse_conv1a(), ...)
+// return the handle's override while the scope is open on this thread, else the process default; and (b) the device memory the handle
+// owns: everything a dim_*_create (or a lazily built debug buffer) allocates goes through dim_dev_alloc / dim_upload* below and is freed
+// by the one dim_handle_release its dim_*_destroy calls.  (Bodies: api_ops.hip.)
 constexpr int DIM_TUNE_KEYS = 19;
 constexpr unsigned DIM_HANDLE_MAGIC = 0x44494d48u;   // "DIMH"
 struct DimTune {
@@ -335,7 +341,38 @@ struct DimTune {
 struct DimHandleBase {
   unsigned magic = DIM_HANDLE_MAGIC;
   DimTune tune;
+  std::vector<void*> allocs;   // device allocations of the handle
+  size_t bytes = 0;            // their requested sizes added up (without the slack)
 };
+// Every allocation gets DIM_ALLOC_SLACK bytes behind its end: kernels with 16-byte loads may read up to the end of a padded row.  A zero
+// count is legal.  On failure: -1, the message names the byte count and says "out of memory" (include/dim_hip.h; capi.check keys on it),
+// and HIP's sticky last error is cleared so that the next DIM_LAUNCH_CHECK on this thread does not report the failed hipMalloc.
+constexpr size_t DIM_ALLOC_SLACK = 256;
+int dim_dev_alloc_bytes(DimHandleBase* b, void** p, size_t bytes);
+template <typename T> int dim_dev_alloc(DimHandleBase* b, T** p, size_t count) {
+  void* q = nullptr;
+  if (dim_dev_alloc_bytes(b, &q, count * sizeof(T)) != 0) return -1;
+  *p = (T*)q;
+  return 0;
+}
+int dim_upload_bytes(DimHandleBase* b, void** dst, const void* src, size_t bytes);   // allocation + blocking host-to-device copy
+template <typename T> int dim_upload(DimHandleBase* b, T** dst, const T* src, size_t count) {
+  void* q = nullptr;
+  if (dim_upload_bytes(b, &q, src, count * sizeof(T)) != 0) return -1;
+  *dst = (T*)q;
+  return 0;
+}
+// fp32 weights: rejected ("non-finite") unless every value is finite
+int dim_upload_f32(DimHandleBase* b, float** dst, const float* src, size_t count);
+inline int dim_upload_f32(DimHandleBase* b, float** dst, const std::vector<float>& v) { return dim_upload_f32(b, dst, v.data(), v.size()); }
+// a matrix-core operand already split on the host (dim_kernels.h: SplitWeights; the splitter has filled scale_off): uploads the planes and
+// sets dev / mode / n_pad.  The caller checks the fp32 source (dim_all_finite) before it splits ...
+struct SplitWeights;
+int dim_upload_split(DimHandleBase* b, SplitWeights* sw, const std::vector<unsigned short>& host, int mode, int n_pad);
+// ... which this does for a [K][N] fp32 GEMM operand: finiteness check, split_weights, dim_upload_split
+int dim_upload_gemm_split(DimHandleBase* b, SplitWeights* sw, const float* w_kn, int K, int N, int n_pad, int mode, int kperm = 0);
+void dim_handle_release(DimHandleBase* b);   // frees the allocations (the handle object itself is the caller's)
+#define DIM_TRY(x) do { if ((x) != 0) return -1; } while (0)   // create functions hold the handle in a std::unique_ptr with its destroy as deleter
 void dim_tune_scope_set(const DimTune* t);     // api_ops.hip (thread-local)
 const DimTune* dim_tune_scope_get();
 struct DimTuneScope {

@@ -90,45 +90,13 @@ struct dim_lg {
   int* done_host = nullptr;            // page-locked, device-mapped: [layers][max_pairs flags | sequence word] written by lg_decide_kernel
   int call_seq = 0;
   LgState st;
-  std::vector<void*> allocs;
 };
 
 namespace {
-template <typename T>
-int dev_alloc(dim_lg* h, T** p, size_t count) {
-  void* q = nullptr;
-  hipError_t e = hipMalloc(&q, count * sizeof(T) + 256);
-  if (e != hipSuccess) {
-    dim_set_error("hipMalloc of %zu bytes failed: out of memory (%s)", count * sizeof(T), hipGetErrorString(e));
-    return -1;
-  }
-  h->allocs.push_back(q);
-  *p = (T*)q;
-  return 0;
-}
-int upload(dim_lg* h, float** dst, const std::vector<float>& v) {
-  if (!dim_all_finite(v.data(), v.size())) { dim_set_error("non-finite value in the weights"); return -1; }
-  if (dev_alloc(h, dst, v.size()) != 0) return -1;
-  if (hipMemcpy(*dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    dim_set_error("weight upload failed");
-    return -1;
-  }
-  return 0;
-}
 // [K][N] fp32 GEMM operand -> device split planes for both split modes
-int upload_x3(dim_lg* h, SplitWeights* dst, const std::vector<float>& w_kn, int K, int N, int kperm = 0) {
-  const int n_pad = (N + 127) / 128 * 128;
-  for (int mode = 1; mode <= 2; ++mode) {
-    std::vector<unsigned short> host(gemm_split_weight_elems(K, n_pad, mode));
-    split_weights(w_kn.data(), K, N, n_pad, mode, host.data(), &dst[mode], kperm);
-    unsigned short* d = nullptr;
-    if (dev_alloc(h, &d, host.size()) != 0) return -1;
-    if (hipMemcpy(d, host.data(), host.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
-      dim_set_error("weight upload failed");
-      return -1;
-    }
-    dst[mode].dev = d; dst[mode].mode = mode; dst[mode].n_pad = n_pad;
-  }
+int upload_x3(DimHandleBase* hb, SplitWeights* dst, const std::vector<float>& w_kn, int K, int N, int kperm = 0) {
+  for (int mode = 1; mode <= 2; ++mode)
+    if (dim_upload_gemm_split(hb, &dst[mode], w_kn.data(), K, N, (N + 127) / 128 * 128, mode, kperm) != 0) return -1;
   return 0;
 }
 // ffn.0([x | out_proj(ctx)]) = x*W1a + (ctx*Wout + bout)*W1b + b1 = [x | ctx] * [W1a ; Wout*W1b] + (b1 + bout*W1b):
@@ -174,7 +142,7 @@ extern "C" {
 
 void dim_lg_destroy(dim_lg* h) {
   if (!h) return;
-  for (void* p : h->allocs) hipFree(p);
+  dim_handle_release(&h->base);
   if (h->done_host) hipHostFree(h->done_host);
   delete h;
 }
@@ -185,17 +153,18 @@ int dim_lg_create(const dim_lg_weights* w, const dim_lg_config* cfg, int max_pai
   DIM_REQUIRE(w->input_dim > 0 && w->input_dim % 32 == 0, "dim_lg_create: input_dim %d must be a multiple of 32", w->input_dim);
   DIM_REQUIRE((w->input_dim == 256) == (w->input_proj_w == nullptr), "dim_lg_create: input_proj must be given iff input_dim != 256 (LGN:361-364)");
   DIM_REQUIRE(max_pairs > 0 && max_kpts > 0, "dim_lg_create: bad sizes");
-  dim_lg* h = new dim_lg();
+  std::unique_ptr<dim_lg, void (*)(dim_lg*)> guard(new dim_lg(), dim_lg_destroy);
+  dim_lg* const h = guard.get();
+  DimHandleBase* const hb = &h->base;
   h->cfg = *cfg;
   h->n_layers = w->n_layers; h->input_dim = w->input_dim; h->max_pairs = max_pairs;
   h->nmax = (max_kpts + 3) & ~3;
   h->inproj_w = h->inproj_b = nullptr;
   h->thr.assign(w->confidence_thresholds, w->confidence_thresholds + w->n_layers);
-#define LG_TRY(x) do { if ((x) != 0) { dim_lg_destroy(h); return -1; } } while (0)
-  LG_TRY(upload(h, &h->Wr, vec(w->posenc_Wr, 64)));
+  DIM_TRY(dim_upload_f32(hb, &h->Wr, vec(w->posenc_Wr, 64)));
   if (w->input_proj_w) {
-    LG_TRY(upload(h, &h->inproj_w, transpose(w->input_proj_w, 256, w->input_dim)));
-    LG_TRY(upload(h, &h->inproj_b, vec(w->input_proj_b, 256)));
+    DIM_TRY(dim_upload_f32(hb, &h->inproj_w, transpose(w->input_proj_w, 256, w->input_dim)));
+    DIM_TRY(dim_upload_f32(hb, &h->inproj_b, vec(w->input_proj_b, 256)));
   }
   h->L.resize(w->n_layers);
   for (int i = 0; i < w->n_layers; ++i) {
@@ -210,11 +179,11 @@ int dim_lg_create(const dim_lg_weights* w, const dim_lg_config* cfg, int max_pai
           qkvb[c] = s.self_Wqkv_b[o];
           for (int k = 0; k < 256; ++k) qkv[(size_t)k * 768 + c] = s.self_Wqkv_w[(size_t)o * 256 + k];
         }
-    LG_TRY(upload(h, &d.qkv_w, qkv)); LG_TRY(upload(h, &d.qkv_b, qkvb)); LG_TRY(upload_x3(h, d.qkv_x, qkv, 256, 768));
-    LG_TRY(upload(h, &d.out_w, transpose(s.self_out_w, 256, 256))); LG_TRY(upload_x3(h, d.out_x, transpose(s.self_out_w, 256, 256), 256, 256)); LG_TRY(upload(h, &d.out_b, vec(s.self_out_b, 256)));
-    LG_TRY(upload(h, &d.sffn0_w, transpose(s.self_ffn0_w, 512, 512))); LG_TRY(upload_x3(h, d.sffn0_x, transpose(s.self_ffn0_w, 512, 512), 512, 512)); LG_TRY(upload(h, &d.sffn0_b, vec(s.self_ffn0_b, 512)));
-    LG_TRY(upload(h, &d.sln_w, vec(s.self_ln_w, 512))); LG_TRY(upload(h, &d.sln_b, vec(s.self_ln_b, 512)));
-    LG_TRY(upload(h, &d.sffn3_w, transpose(s.self_ffn3_w, 256, 512))); LG_TRY(upload_x3(h, d.sffn3_x, transpose(s.self_ffn3_w, 256, 512), 512, 256)); LG_TRY(upload(h, &d.sffn3_b, vec(s.self_ffn3_b, 256)));
+    DIM_TRY(dim_upload_f32(hb, &d.qkv_w, qkv)); DIM_TRY(dim_upload_f32(hb, &d.qkv_b, qkvb)); DIM_TRY(upload_x3(hb, d.qkv_x, qkv, 256, 768));
+    DIM_TRY(dim_upload_f32(hb, &d.out_w, transpose(s.self_out_w, 256, 256))); DIM_TRY(upload_x3(hb, d.out_x, transpose(s.self_out_w, 256, 256), 256, 256)); DIM_TRY(dim_upload_f32(hb, &d.out_b, vec(s.self_out_b, 256)));
+    DIM_TRY(dim_upload_f32(hb, &d.sffn0_w, transpose(s.self_ffn0_w, 512, 512))); DIM_TRY(upload_x3(hb, d.sffn0_x, transpose(s.self_ffn0_w, 512, 512), 512, 512)); DIM_TRY(dim_upload_f32(hb, &d.sffn0_b, vec(s.self_ffn0_b, 512)));
+    DIM_TRY(dim_upload_f32(hb, &d.sln_w, vec(s.self_ln_w, 512))); DIM_TRY(dim_upload_f32(hb, &d.sln_b, vec(s.self_ln_b, 512)));
+    DIM_TRY(dim_upload_f32(hb, &d.sffn3_w, transpose(s.self_ffn3_w, 256, 512))); DIM_TRY(upload_x3(hb, d.sffn3_x, transpose(s.self_ffn3_w, 256, 512), 512, 256)); DIM_TRY(dim_upload_f32(hb, &d.sffn3_b, vec(s.self_ffn3_b, 256)));
     // to_qk and to_v fused into one [256][512] operand: columns [qk | v]
     std::vector<float> cq((size_t)256 * 512), cqb(512);
     for (int o = 0; o < 256; ++o) {
@@ -224,25 +193,25 @@ int dim_lg_create(const dim_lg_weights* w, const dim_lg_config* cfg, int max_pai
         cq[(size_t)k * 512 + 256 + o] = s.cross_v_w[(size_t)o * 256 + k];
       }
     }
-    LG_TRY(upload(h, &d.cqkv_w, cq)); LG_TRY(upload(h, &d.cqkv_b, cqb)); LG_TRY(upload_x3(h, d.cqkv_x, cq, 256, 512));
-    LG_TRY(upload(h, &d.cout_w, transpose(s.cross_out_w, 256, 256))); LG_TRY(upload_x3(h, d.cout_x, transpose(s.cross_out_w, 256, 256), 256, 256)); LG_TRY(upload(h, &d.cout_b, vec(s.cross_out_b, 256)));
-    LG_TRY(upload(h, &d.cffn0_w, transpose(s.cross_ffn0_w, 512, 512))); LG_TRY(upload_x3(h, d.cffn0_x, transpose(s.cross_ffn0_w, 512, 512), 512, 512)); LG_TRY(upload(h, &d.cffn0_b, vec(s.cross_ffn0_b, 512)));
-    LG_TRY(upload(h, &d.cln_w, vec(s.cross_ln_w, 512))); LG_TRY(upload(h, &d.cln_b, vec(s.cross_ln_b, 512)));
-    LG_TRY(upload(h, &d.cffn3_w, transpose(s.cross_ffn3_w, 256, 512))); LG_TRY(upload_x3(h, d.cffn3_x, transpose(s.cross_ffn3_w, 256, 512), 512, 256)); LG_TRY(upload(h, &d.cffn3_b, vec(s.cross_ffn3_b, 256)));
+    DIM_TRY(dim_upload_f32(hb, &d.cqkv_w, cq)); DIM_TRY(dim_upload_f32(hb, &d.cqkv_b, cqb)); DIM_TRY(upload_x3(hb, d.cqkv_x, cq, 256, 512));
+    DIM_TRY(dim_upload_f32(hb, &d.cout_w, transpose(s.cross_out_w, 256, 256))); DIM_TRY(upload_x3(hb, d.cout_x, transpose(s.cross_out_w, 256, 256), 256, 256)); DIM_TRY(dim_upload_f32(hb, &d.cout_b, vec(s.cross_out_b, 256)));
+    DIM_TRY(dim_upload_f32(hb, &d.cffn0_w, transpose(s.cross_ffn0_w, 512, 512))); DIM_TRY(upload_x3(hb, d.cffn0_x, transpose(s.cross_ffn0_w, 512, 512), 512, 512)); DIM_TRY(dim_upload_f32(hb, &d.cffn0_b, vec(s.cross_ffn0_b, 512)));
+    DIM_TRY(dim_upload_f32(hb, &d.cln_w, vec(s.cross_ln_w, 512))); DIM_TRY(dim_upload_f32(hb, &d.cln_b, vec(s.cross_ln_b, 512)));
+    DIM_TRY(dim_upload_f32(hb, &d.cffn3_w, transpose(s.cross_ffn3_w, 256, 512))); DIM_TRY(upload_x3(hb, d.cffn3_x, transpose(s.cross_ffn3_w, 256, 512), 512, 256)); DIM_TRY(dim_upload_f32(hb, &d.cffn3_b, vec(s.cross_ffn3_b, 256)));
     {
       std::vector<float> wf, bf;
       fold_out_proj(transpose(s.self_out_w, 256, 256), vec(s.self_out_b, 256), transpose(s.self_ffn0_w, 512, 512), vec(s.self_ffn0_b, 512), wf, bf);
-      LG_TRY(upload_x3(h, d.sffn0f_x, wf, 512, 512)); LG_TRY(upload(h, &d.sffn0f_b, bf));
+      DIM_TRY(upload_x3(hb, d.sffn0f_x, wf, 512, 512)); DIM_TRY(dim_upload_f32(hb, &d.sffn0f_b, bf));
       fold_out_proj(transpose(s.cross_out_w, 256, 256), vec(s.cross_out_b, 256), transpose(s.cross_ffn0_w, 512, 512), vec(s.cross_ffn0_b, 512), wf, bf);
-      LG_TRY(upload_x3(h, d.cffn0f_x, wf, 512, 512)); LG_TRY(upload(h, &d.cffn0f_b, bf));
-      LG_TRY(upload_x3(h, d.sffn3p_x, transpose(s.self_ffn3_w, 256, 512), 512, 256, 1));
-      LG_TRY(upload_x3(h, d.cffn3p_x, transpose(s.cross_ffn3_w, 256, 512), 512, 256, 1));
+      DIM_TRY(upload_x3(hb, d.cffn0f_x, wf, 512, 512)); DIM_TRY(dim_upload_f32(hb, &d.cffn0f_b, bf));
+      DIM_TRY(upload_x3(hb, d.sffn3p_x, transpose(s.self_ffn3_w, 256, 512), 512, 256, 1));
+      DIM_TRY(upload_x3(hb, d.cffn3p_x, transpose(s.cross_ffn3_w, 256, 512), 512, 256, 1));
     }
-    LG_TRY(upload(h, &d.match_w, vec(s.assign_match_w, 256))); LG_TRY(upload(h, &d.match_b, vec(s.assign_match_b, 1)));
+    DIM_TRY(dim_upload_f32(hb, &d.match_w, vec(s.assign_match_w, 256))); DIM_TRY(dim_upload_f32(hb, &d.match_b, vec(s.assign_match_b, 1)));
     // final_proj / d^0.25 (LGN:268-270): 256^0.25 = 4, a power of two -> folding the scale is exact
-    LG_TRY(upload(h, &d.proj_w, transpose(s.assign_proj_w, 256, 256, 0.25f))); LG_TRY(upload_x3(h, d.proj_x, transpose(s.assign_proj_w, 256, 256, 0.25f), 256, 256)); LG_TRY(upload(h, &d.proj_b, vec(s.assign_proj_b, 256, 0.25f)));
+    DIM_TRY(dim_upload_f32(hb, &d.proj_w, transpose(s.assign_proj_w, 256, 256, 0.25f))); DIM_TRY(upload_x3(hb, d.proj_x, transpose(s.assign_proj_w, 256, 256, 0.25f), 256, 256)); DIM_TRY(dim_upload_f32(hb, &d.proj_b, vec(s.assign_proj_b, 256, 0.25f)));
     d.tok_w = d.tok_b = nullptr;
-    if (s.token_w) { LG_TRY(upload(h, &d.tok_w, vec(s.token_w, 256))); LG_TRY(upload(h, &d.tok_b, vec(s.token_b, 1))); }
+    if (s.token_w) { DIM_TRY(dim_upload_f32(hb, &d.tok_w, vec(s.token_w, 256))); DIM_TRY(dim_upload_f32(hb, &d.tok_b, vec(s.token_b, 1))); }
     DIM_REQUIRE(i == w->n_layers - 1 || s.token_w, "dim_lg_create: token_confidence.%d missing", i);
   }
   {
@@ -251,14 +220,11 @@ int dim_lg_create(const dim_lg_weights* w, const dim_lg_config* cfg, int max_pai
       memcpy(&mw[(size_t)i * 256], w->layers[i].assign_match_w, 256 * sizeof(float));
       mb[i] = w->layers[i].assign_match_b[0];
     }
-    LG_TRY(upload(h, &h->match_w_all, mw)); LG_TRY(upload(h, &h->match_b_all, mb));
+    DIM_TRY(dim_upload_f32(hb, &h->match_w_all, mw)); DIM_TRY(dim_upload_f32(hb, &h->match_b_all, mb));
     for (int mode = 1; mode <= 2; ++mode) {
       std::vector<GemmLayerTab> tab(w->n_layers);
       for (int i = 0; i < w->n_layers; ++i) tab[i] = GemmLayerTab{h->L[i].proj_x[mode].dev, h->L[i].proj_x[mode].inv_ch(), h->L[i].proj_b};
-      LG_TRY(dev_alloc(h, &h->proj_tab[mode], tab.size()));
-      if (hipMemcpy(h->proj_tab[mode], tab.data(), tab.size() * sizeof(GemmLayerTab), hipMemcpyHostToDevice) != hipSuccess) {
-        dim_set_error("weight upload failed"); dim_lg_destroy(h); return -1;
-      }
+      DIM_TRY(dim_upload(hb, &h->proj_tab[mode], tab.data(), tab.size()));
     }
   }
   if (max_pairs <= FOLLOW_MAX_PAIRS) {
@@ -274,22 +240,21 @@ int dim_lg_create(const dim_lg_weights* w, const dim_lg_config* cfg, int max_pai
   LgState& st = h->st;
   const size_t P = max_pairs, I = 2 * P, N = h->nmax;
   st.n_pairs = max_pairs; st.n_items = 2 * max_pairs; st.nmax = h->nmax; st.nsel = h->nmax;
-  LG_TRY(dev_alloc(h, &st.desc, I * N * 256)); LG_TRY(dev_alloc(h, &st.enc, I * N * 64));
-  LG_TRY(dev_alloc(h, &st.qkv, I * N * 768)); LG_TRY(dev_alloc(h, &st.ctx, I * N * 256));
-  LG_TRY(dev_alloc(h, &st.msg, I * N * 256)); LG_TRY(dev_alloc(h, &st.hid, I * N * 512));
-  LG_TRY(dev_alloc(h, &st.md, I * N * 256)); LG_TRY(dev_alloc(h, &st.sim, P * N * N));
-  LG_TRY(dev_alloc(h, &st.conf, I * N)); LG_TRY(dev_alloc(h, &st.mtch, I * N)); LG_TRY(dev_alloc(h, &st.zls, I * N));
-  LG_TRY(dev_alloc(h, &st.rmax, I * N)); LG_TRY(dev_alloc(h, &st.rlse, I * N)); LG_TRY(dev_alloc(h, &st.best, I * N));
-  LG_TRY(dev_alloc(h, &st.arg, I * N)); LG_TRY(dev_alloc(h, &st.n_cur, I)); LG_TRY(dev_alloc(h, &st.n_new, I));
-  LG_TRY(dev_alloc(h, &st.n_orig, I)); LG_TRY(dev_alloc(h, &st.ind, I * N)); LG_TRY(dev_alloc(h, &st.dest, I * N));
-  LG_TRY(dev_alloc(h, &st.prune, I * N)); LG_TRY(dev_alloc(h, &st.done, P)); LG_TRY(dev_alloc(h, &st.cnt_lt, P));
-  { unsigned char* kvp = nullptr; LG_TRY(dev_alloc(h, &kvp, I * 4 * ((N + 31) / 32) * 1536 * 16)); st.kv_img = kvp; }
+  DIM_TRY(dim_dev_alloc(hb, &st.desc, I * N * 256)); DIM_TRY(dim_dev_alloc(hb, &st.enc, I * N * 64));
+  DIM_TRY(dim_dev_alloc(hb, &st.qkv, I * N * 768)); DIM_TRY(dim_dev_alloc(hb, &st.ctx, I * N * 256));
+  DIM_TRY(dim_dev_alloc(hb, &st.msg, I * N * 256)); DIM_TRY(dim_dev_alloc(hb, &st.hid, I * N * 512));
+  DIM_TRY(dim_dev_alloc(hb, &st.md, I * N * 256)); DIM_TRY(dim_dev_alloc(hb, &st.sim, P * N * N));
+  DIM_TRY(dim_dev_alloc(hb, &st.conf, I * N)); DIM_TRY(dim_dev_alloc(hb, &st.mtch, I * N)); DIM_TRY(dim_dev_alloc(hb, &st.zls, I * N));
+  DIM_TRY(dim_dev_alloc(hb, &st.rmax, I * N)); DIM_TRY(dim_dev_alloc(hb, &st.rlse, I * N)); DIM_TRY(dim_dev_alloc(hb, &st.best, I * N));
+  DIM_TRY(dim_dev_alloc(hb, &st.arg, I * N)); DIM_TRY(dim_dev_alloc(hb, &st.n_cur, I)); DIM_TRY(dim_dev_alloc(hb, &st.n_new, I));
+  DIM_TRY(dim_dev_alloc(hb, &st.n_orig, I)); DIM_TRY(dim_dev_alloc(hb, &st.ind, I * N)); DIM_TRY(dim_dev_alloc(hb, &st.dest, I * N));
+  DIM_TRY(dim_dev_alloc(hb, &st.prune, I * N)); DIM_TRY(dim_dev_alloc(hb, &st.done, P)); DIM_TRY(dim_dev_alloc(hb, &st.cnt_lt, P));
+  { unsigned char* kvp = nullptr; DIM_TRY(dim_dev_alloc(hb, &kvp, I * 4 * ((N + 31) / 32) * 1536 * 16)); st.kv_img = kvp; }
   st.attn_part_items = (int)(I < 8 ? I : 8);  // key-split attention only pays for <= 4 pairs
   if (dim_attn_probe()) st.attn_part_items = (int)I;   // timing probes (dim_tune_set key 12): 16 partial records per row for every item
-  LG_TRY(dev_alloc(h, &st.attn_part, (size_t)st.attn_part_items * 4 * N * (dim_attn_probe() ? 16 : 4) * 68));
-  LG_TRY(dev_alloc(h, &st.tdesc, I * N * 256)); LG_TRY(dev_alloc(h, &st.tenc, I * N * 64)); LG_TRY(dev_alloc(h, &st.tind, I * N));
-#undef LG_TRY
-  *out = h;
+  DIM_TRY(dim_dev_alloc(hb, &st.attn_part, (size_t)st.attn_part_items * 4 * N * (dim_attn_probe() ? 16 : 4) * 68));
+  DIM_TRY(dim_dev_alloc(hb, &st.tdesc, I * N * 256)); DIM_TRY(dim_dev_alloc(hb, &st.tenc, I * N * 64)); DIM_TRY(dim_dev_alloc(hb, &st.tind, I * N));
+  *out = guard.release();
   return 0;
 }
 

@@ -384,30 +384,15 @@ struct dim_nn {
   DimHandleBase base;
   dim_nn_config cfg;
   int max_pairs = 0, nk = 0, dim = 0, T = 0;
-  std::vector<void*> allocs;
-  size_t bytes = 0;
   int* owner = nullptr;
   float *norms = nullptr, *rp = nullptr, *cp = nullptr, *fin = nullptr;
 };
-
-template <typename T> static int nn_alloc(dim_nn* h, T** p, size_t count) {
-  void* q = nullptr;
-  if (hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
-    (void)hipGetLastError();
-    dim_set_error("dim_nn_create: hipMalloc of %zu bytes failed: out of memory", count * sizeof(T));
-    return -1;
-  }
-  h->allocs.push_back(q);
-  h->bytes += count * sizeof(T);
-  *p = (T*)q;
-  return 0;
-}
 
 extern "C" {
 
 void dim_nn_destroy(dim_nn* h) {
   if (!h) return;
-  for (void* p : h->allocs) hipFree(p);
+  dim_handle_release(&h->base);
   delete h;
 }
 
@@ -416,23 +401,22 @@ int dim_nn_create(const dim_nn_config* cfg, int max_pairs, int max_kpts, int dim
   DIM_REQUIRE(cfg->mode >= DIM_NN_MODE_NN && cfg->mode <= DIM_NN_MODE_SMNN, "dim_nn_create: mode %d (0 nn, 1 mnn, 2 snn, 3 smnn)", cfg->mode);
   DIM_REQUIRE(max_pairs > 0 && max_kpts > 0, "dim_nn_create: bad sizes");
   DIM_REQUIRE(dim >= 64 && dim % 64 == 0, "dim_nn_create: descriptor dimension %d must be a multiple of 64", dim);
-  dim_nn* h = new dim_nn();
+  std::unique_ptr<dim_nn, void (*)(dim_nn*)> guard(new dim_nn(), dim_nn_destroy);
+  dim_nn* const h = guard.get();
+  DimHandleBase* const hb = &h->base;
   h->cfg = *cfg;
   h->max_pairs = max_pairs; h->dim = dim;
   h->nk = (max_kpts + 3) & ~3;
   h->T = cdiv(h->nk, BT);
   const size_t P = max_pairs, NK = h->nk, T = h->T;
-  if (nn_alloc(h, &h->owner, 2 * P) || nn_alloc(h, &h->norms, 2 * P * NK) || nn_alloc(h, &h->rp, P * T * 3 * NK) ||
-      nn_alloc(h, &h->cp, P * T * 3 * NK) || nn_alloc(h, &h->fin, P * 2 * 3 * NK)) {
-    dim_nn_destroy(h);
-    return -1;
-  }
-  *out = h;
+  DIM_TRY(dim_dev_alloc(hb, &h->owner, 2 * P)); DIM_TRY(dim_dev_alloc(hb, &h->norms, 2 * P * NK)); DIM_TRY(dim_dev_alloc(hb, &h->rp, P * T * 3 * NK));
+  DIM_TRY(dim_dev_alloc(hb, &h->cp, P * T * 3 * NK)); DIM_TRY(dim_dev_alloc(hb, &h->fin, P * 2 * 3 * NK));
+  *out = guard.release();
   return 0;
 }
 
 int dim_nn_max_kpts(dim_nn* h) { return h ? h->nk : 0; }
-size_t dim_nn_workspace_bytes(dim_nn* h) { return h ? h->bytes : 0; }
+size_t dim_nn_workspace_bytes(dim_nn* h) { return h ? h->base.bytes : 0; }
 
 int dim_nn_match(dim_nn* h, const float* desc_tab_dev, const int32_t* n_tab_dev, int cap, int desc_is_f16_exact, const int32_t* pair_idx_dev,
                  int n_pairs, int64_t* matches_dev, float* dists_dev, int32_t* n_matches_dev, float* row_stats_dev, float* col_stats_dev,

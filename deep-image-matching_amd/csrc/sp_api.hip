@@ -34,33 +34,19 @@ struct dim_sp {
   bool head_fused;    // the last extract ran convPb + softmax + depth-to-space as one kernel: h->logits is stale
   float* b1_dbg;      // fp32 copy of conv1b's pooled output (dim_sp_debug_conv1b)
   float* x_dbg;       // fp32 copy of it, built on request by dim_sp_debug_buffers
-  std::vector<void*> allocs;
 };
 
 namespace {
 const int kCin[12] = {1, 64, 64, 64, 64, 128, 128, 128, 128, 256, 128, 256};
 const int kCout[12] = {64, 64, 64, 64, 128, 128, 128, 128, 256, 65, 256, 256};
 const int kK[12] = {3, 3, 3, 3, 3, 3, 3, 3, 3, 1, 3, 1};
-
-template <typename T>
-int dev_alloc(dim_sp* h, T** p, size_t count) {
-  void* q = nullptr;
-  hipError_t e = hipMalloc(&q, count * sizeof(T) + 256);
-  if (e != hipSuccess) {
-    dim_set_error("hipMalloc of %zu bytes failed: out of memory (%s)", count * sizeof(T), hipGetErrorString(e));
-    return -1;
-  }
-  h->allocs.push_back(q);
-  *p = (T*)q;
-  return 0;
-}
 }  // namespace
 
 extern "C" {
 
 void dim_sp_destroy(dim_sp* h) {
   if (!h) return;
-  for (void* p : h->allocs) hipFree(p);
+  dim_handle_release(&h->base);
   delete h;
 }
 
@@ -71,18 +57,20 @@ int dim_sp_create(const dim_sp_weights* w, const dim_sp_config* cfg, int max_bat
   DIM_REQUIRE(cfg->max_keypoints != 0 && cfg->max_keypoints >= -1, "\"max_keypoints\" must be positive or \"-1\"");  // SPN:152-154
   DIM_REQUIRE(capacity > 0 && capacity >= cfg->max_keypoints, "dim_sp_create: capacity %d < max_keypoints %d", capacity, cfg->max_keypoints);
   DIM_REQUIRE(cfg->nms_radius >= 0, "nms_radius must be >= 0");  // SPN:49
-  dim_sp* h = new dim_sp();
+  std::unique_ptr<dim_sp, void (*)(dim_sp*)> guard(new dim_sp(), dim_sp_destroy);
+  dim_sp* const h = guard.get();
+  DimHandleBase* const hb = &h->base;
   memset((void*)&h->cfg, 0, sizeof(h->cfg));
   h->cfg = *cfg;
   h->max_batch = max_batch; h->max_h = max_h; h->max_w = max_w; h->capacity = capacity;
   h->last_h = h->last_w = h->last_batch = 0;
   h->b1_dbg = nullptr; h->x_dbg = nullptr; h->head_fused = false;
-#define SP_TRY(x) do { if ((x) != 0) { dim_sp_destroy(h); return -1; } } while (0)
   // ---- weights: OIHW (SPN:128-143) -> [tap][cin][cout] / [cin][cout_padded4] ----
   for (int l = 0; l < 12; ++l) {
     const int ci = kCin[l], co = kCout[l], k = kK[l];
     const int co_pad = (co + 3) & ~3;
-    if (!dim_all_finite(w->conv_w[l], (size_t)k * k * ci * co) || !dim_all_finite(w->conv_b[l], (size_t)co)) { dim_set_error("dim_sp_create: non-finite value in the weights of layer %d", l); dim_sp_destroy(h); return -1; }
+    // (checked here for every form below: the conv splits take the OIHW tensor itself)
+    if (!dim_all_finite(w->conv_w[l], (size_t)k * k * ci * co) || !dim_all_finite(w->conv_b[l], (size_t)co)) { dim_set_error("dim_sp_create: non-finite value in the weights of layer %d", l); return -1; }
     std::vector<float> host((size_t)k * k * ci * co_pad, 0.0f);
     for (int o = 0; o < co; ++o)
       for (int i = 0; i < ci; ++i)
@@ -92,10 +80,7 @@ int dim_sp_create(const dim_sp_weights* w, const dim_sp_config* cfg, int max_bat
         std::vector<unsigned short> hx(conv_split_weight_elems(ci, co, mode));
         SplitWeights& sw = h->wsp[mode][l];
         prepare_conv_weights_split(w->conv_w[l], ci, co, mode, hx.data(), &sw);
-        unsigned short* d = nullptr;
-        SP_TRY(dev_alloc(h, &d, hx.size()));
-        if (hipMemcpy(d, hx.data(), hx.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { dim_set_error("weight upload failed"); dim_sp_destroy(h); return -1; }
-        sw.dev = d; sw.mode = mode;
+        DIM_TRY(dim_upload_split(hb, &sw, hx, mode, sw.n_pad));
       }
     }
 #ifdef DIM_RESEARCH
@@ -103,33 +88,19 @@ int dim_sp_create(const dim_sp_weights* w, const dim_sp_config* cfg, int max_bat
       std::vector<unsigned short> hx(conv_wino_weight_elems(ci, co));
       SplitWeights& sw = h->wsw[l];
       prepare_conv_weights_wino(w->conv_w[l], ci, co, hx.data(), &sw);
-      unsigned short* d = nullptr;
-      SP_TRY(dev_alloc(h, &d, hx.size()));
-      if (hipMemcpy(d, hx.data(), hx.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { dim_set_error("weight upload failed"); dim_sp_destroy(h); return -1; }
-      sw.dev = d; sw.mode = 2;
+      DIM_TRY(dim_upload_split(hb, &sw, hx, 2, sw.n_pad));
     }
 #endif
     if (k == 1) {  // the two 1x1 heads (convPb 256 -> 65, convDb 256 -> 256) run on the split GEMM
       std::vector<float> kn((size_t)ci * co);
       for (int o = 0; o < co; ++o)
         for (int i = 0; i < ci; ++i) kn[(size_t)i * co + o] = w->conv_w[l][(size_t)o * ci + i];
-      const int n_pad = (co + 127) / 128 * 128;
-      for (int mode = 1; mode <= 2; ++mode) {
-        std::vector<unsigned short> hx(gemm_split_weight_elems(ci, n_pad, mode));
-        SplitWeights& sw = h->wsp[mode][l];
-        split_weights(kn.data(), ci, co, n_pad, mode, hx.data(), &sw);
-        unsigned short* d = nullptr;
-        SP_TRY(dev_alloc(h, &d, hx.size()));
-        if (hipMemcpy(d, hx.data(), hx.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { dim_set_error("weight upload failed"); dim_sp_destroy(h); return -1; }
-        sw.dev = d; sw.mode = mode; sw.n_pad = n_pad;
-      }
+      for (int mode = 1; mode <= 2; ++mode) DIM_TRY(dim_upload_gemm_split(hb, &h->wsp[mode][l], kn.data(), ci, co, (co + 127) / 128 * 128, mode));
     }
-    SP_TRY(dev_alloc(h, &h->wk[l], host.size()));
-    if (hipMemcpy(h->wk[l], host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { dim_set_error("weight upload failed"); dim_sp_destroy(h); return -1; }
-    std::vector<float> hb(co_pad, 0.0f);
-    memcpy(hb.data(), w->conv_b[l], co * sizeof(float));
-    SP_TRY(dev_alloc(h, &h->bias[l], hb.size()));
-    if (hipMemcpy(h->bias[l], hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { dim_set_error("bias upload failed"); dim_sp_destroy(h); return -1; }
+    DIM_TRY(dim_upload_f32(hb, &h->wk[l], host));
+    std::vector<float> bv(co_pad, 0.0f);
+    memcpy(bv.data(), w->conv_b[l], co * sizeof(float));
+    DIM_TRY(dim_upload_f32(hb, &h->bias[l], bv));
   }
   h->conv1a_bound = 0.0f;
   for (int o = 0; o < 64; ++o) {
@@ -141,28 +112,27 @@ int dim_sp_create(const dim_sp_weights* w, const dim_sp_config* cfg, int max_bat
   const size_t B = max_batch, H = max_h, W = max_w;
   const size_t H2 = H / 2, W2 = W / 2, H4 = H2 / 2, W4 = W2 / 2, hh = H4 / 2, ww = W4 / 2;
   h->a1 = nullptr;  // conv1a's 64-channel full-resolution map: only the unfused A/B path needs it, allocated on first use
-  SP_TRY(dev_alloc(h, &h->b1, B * dim_planes_image_pixels(H2, W2) * 64));
-  SP_TRY(dev_alloc(h, &h->a2, B * dim_planes_image_pixels(H2, W2) * 64));
-  SP_TRY(dev_alloc(h, &h->b2, B * dim_planes_image_pixels(H4, W4) * 64));
-  SP_TRY(dev_alloc(h, &h->a3, B * dim_planes_image_pixels(H4, W4) * 128));
-  SP_TRY(dev_alloc(h, &h->b3, B * dim_planes_image_pixels(hh, ww) * 128));
-  SP_TRY(dev_alloc(h, &h->a4, B * dim_planes_image_pixels(hh, ww) * 128));
-  SP_TRY(dev_alloc(h, &h->x, B * dim_planes_image_pixels(hh, ww) * 128));
-  SP_TRY(dev_alloc(h, &h->pa, B * hh * ww * 256));
-  SP_TRY(dev_alloc(h, &h->logits, B * hh * ww * 65));
-  SP_TRY(dev_alloc(h, &h->da, B * hh * ww * 256));
-  SP_TRY(dev_alloc(h, &h->dd, B * hh * ww * 256));
-  SP_TRY(dev_alloc(h, &h->smap, B * hh * ww * 64));
-  SP_TRY(dev_alloc(h, &h->nms, B * hh * ww * 64));
-  SP_TRY(dev_alloc(h, &h->cand_score, B * hh * ww * 64));
-  SP_TRY(dev_alloc(h, &h->cand_idx, B * hh * ww * 64));
-  SP_TRY(dev_alloc(h, &h->rowcount, B * hh * 8));
-  SP_TRY(dev_alloc(h, &h->rowoff, B * hh * 8));
-  SP_TRY(dev_alloc(h, &h->ncand, B));
+  DIM_TRY(dim_dev_alloc(hb, &h->b1, B * dim_planes_image_pixels(H2, W2) * 64));
+  DIM_TRY(dim_dev_alloc(hb, &h->a2, B * dim_planes_image_pixels(H2, W2) * 64));
+  DIM_TRY(dim_dev_alloc(hb, &h->b2, B * dim_planes_image_pixels(H4, W4) * 64));
+  DIM_TRY(dim_dev_alloc(hb, &h->a3, B * dim_planes_image_pixels(H4, W4) * 128));
+  DIM_TRY(dim_dev_alloc(hb, &h->b3, B * dim_planes_image_pixels(hh, ww) * 128));
+  DIM_TRY(dim_dev_alloc(hb, &h->a4, B * dim_planes_image_pixels(hh, ww) * 128));
+  DIM_TRY(dim_dev_alloc(hb, &h->x, B * dim_planes_image_pixels(hh, ww) * 128));
+  DIM_TRY(dim_dev_alloc(hb, &h->pa, B * hh * ww * 256));
+  DIM_TRY(dim_dev_alloc(hb, &h->logits, B * hh * ww * 65));
+  DIM_TRY(dim_dev_alloc(hb, &h->da, B * hh * ww * 256));
+  DIM_TRY(dim_dev_alloc(hb, &h->dd, B * hh * ww * 256));
+  DIM_TRY(dim_dev_alloc(hb, &h->smap, B * hh * ww * 64));
+  DIM_TRY(dim_dev_alloc(hb, &h->nms, B * hh * ww * 64));
+  DIM_TRY(dim_dev_alloc(hb, &h->cand_score, B * hh * ww * 64));
+  DIM_TRY(dim_dev_alloc(hb, &h->cand_idx, B * hh * ww * 64));
+  DIM_TRY(dim_dev_alloc(hb, &h->rowcount, B * hh * 8));
+  DIM_TRY(dim_dev_alloc(hb, &h->rowoff, B * hh * 8));
+  DIM_TRY(dim_dev_alloc(hb, &h->ncand, B));
   h->topk_keys = nullptr;
-  if (topk_scratch_keys(max_batch, cfg->max_keypoints)) SP_TRY(dev_alloc(h, &h->topk_keys, topk_scratch_keys(max_batch, cfg->max_keypoints)));
-#undef SP_TRY
-  *out = h;
+  if (topk_scratch_keys(max_batch, cfg->max_keypoints)) DIM_TRY(dim_dev_alloc(hb, &h->topk_keys, topk_scratch_keys(max_batch, cfg->max_keypoints)));
+  *out = guard.release();
   return 0;
 }
 
@@ -206,7 +176,7 @@ int dim_sp_extract(dim_sp* h, const float* images_dev, int batch, int H, int W, 
   if (x6 && dim_fuse_conv1a()) {  // conv1a evaluated inside conv1b's halo staging: its 64-channel full-resolution map never exists
     SP_SITE(DIM_PROF_SP_CONV1B, launch_conv3x3_x6_fused1a(images_dev, h->wk[0], h->bias[0], h->wsp[pmode][1], h->bias[1], h->b1, batch, H, W, 64, 1, 1, planes ? 1 : 0, s, sat_enc, sat_img));
   } else {
-    if (!h->a1) SP_RUN(dev_alloc(h, &h->a1, (size_t)h->max_batch * h->max_h * h->max_w * 64));
+    if (!h->a1) SP_RUN(dim_dev_alloc(&h->base, &h->a1, (size_t)h->max_batch * h->max_h * h->max_w * 64));
     SP_SITE(DIM_PROF_SP_CONV1A, launch_conv1a(images_dev, h->wk[0], h->bias[0], h->a1, batch, H, W, s));
     SP_SITE(DIM_PROF_SP_CONV1B, conv(1, h->a1, h->b1, H, W, 64, 64, 1));
   }
@@ -274,7 +244,7 @@ int dim_sp_debug_buffers(dim_sp* h, const float** encoder, const float** logits,
   if (encoder) {
     *encoder = h->x;
     if (h->x_is_planes) {  // rebuild fp32 from the planes of the last batch
-      if (!h->x_dbg && dev_alloc(h, &h->x_dbg, (size_t)h->max_batch * (h->max_h / 8) * (h->max_w / 8) * 128) != 0) return -1;
+      if (!h->x_dbg && dim_dev_alloc(&h->base, &h->x_dbg, (size_t)h->max_batch * (h->max_h / 8) * (h->max_w / 8) * 128) != 0) return -1;
       if (launch_planes_to_f32(h->x, h->last_batch, h->last_h * h->last_w, 128, h->x_dbg, nullptr) != 0) return -1;
       DIM_HIP(hipDeviceSynchronize());
       *encoder = h->x_dbg;
@@ -304,7 +274,7 @@ int dim_sp_debug_conv1b(dim_sp* h, int batch, int H, int W, const float** out_f3
   DIM_REQUIRE(h && out_f32 && batch >= 1 && batch <= h->max_batch, "dim_sp_debug_conv1b: bad argument");
   DimTuneScope tune_scope(&h->base);
   const int H2 = H / 2, W2 = W / 2;
-  if (!h->b1_dbg && dev_alloc(h, &h->b1_dbg, (size_t)h->max_batch * (h->max_h / 2) * (h->max_w / 2) * 64) != 0) return -1;
+  if (!h->b1_dbg && dim_dev_alloc(&h->base, &h->b1_dbg, (size_t)h->max_batch * (h->max_h / 2) * (h->max_w / 2) * 64) != 0) return -1;
   const bool planes = dim_precision_mode() == 2 && dim_fuse_conv1a() && dim_presplit_activations();
   if (planes) {
     if (launch_planes_to_f32(h->b1, batch, H2 * W2, 64, h->b1_dbg, nullptr) != 0) return -1;

@@ -47,29 +47,19 @@ class _LgConfig(ctypes.Structure):
                 ("filter_threshold", ctypes.c_double), ("pruning_min_kpts", ctypes.c_int)]
 
 
-class LightGlueHIP:
+class LightGlueHIP(capi.ResidentHandle):
     """Resident LightGlue on one GPU.  conf keys follow LightGlue._default_conf (LGN:301-314)."""
 
+    _destroy = "dim_lg_destroy"
     default_conf = {"n_layers": 9, "depth_confidence": 0.95, "width_confidence": 0.99, "filter_threshold": 0.1,
                     "pruning_min_kpts": -1}
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], conf: Optional[dict] = None, max_pairs: int = 1,
                  max_kpts: int = 2048, device="cuda", lib=None, on_saturation: str = "fallback", arithmetic=None):
         self.conf = {**self.default_conf, **(conf or {})}
-        self.arithmetic = arithmetic        # None: the process default; "fp16x3" | "bf16x6" | "fp32": this handle only
-        self.on_saturation = on_saturation  # fp16x3 range guard policy of __call__: "fallback" (bf16x6 re-run) | "raise" | "off"
-        self.lib = lib if lib is not None else capi.load()
-        self.device = torch.device(device)
-        if lib is None and self.device.type != "cuda":
-            raise capi.DimHipError("LightGlueHIP needs a HIP device; there is no CPU fallback")
+        self._open(device, lib, on_saturation, arithmetic)
         L = int(self.conf["n_layers"])
-        keep = []
-
-        def host(name):
-            t = state_dict[name].detach().float().contiguous().cpu()
-            keep.append(t)
-            return t.data_ptr()
-
+        host = lambda name: self._host(state_dict[name])
         self.input_dim = int(state_dict["input_proj.weight"].shape[1]) if "input_proj.weight" in state_dict else 256
         layers = (_LgLayer * L)()
         for i in range(L):
@@ -86,34 +76,12 @@ class LightGlueHIP:
         c = _LgConfig(float(self.conf["depth_confidence"]), float(self.conf["width_confidence"]),
                       float(self.conf["filter_threshold"]), int(self.conf["pruning_min_kpts"]))
         self.max_pairs = int(max_pairs)
-        self._h = ctypes.c_void_p()
-        with self._ctx():
-            capi.check(self.lib, self.lib.dim_lg_create(ctypes.byref(w), ctypes.byref(c), self.max_pairs, int(max_kpts), ctypes.byref(self._h)))
+        self._create(self.lib.dim_lg_create, ctypes.byref(w), ctypes.byref(c), self.max_pairs, int(max_kpts))
         self.nk = self.lib.dim_lg_max_kpts(self._h)
-        if arithmetic is not None:
-            capi.set_handle_arithmetic(self.lib, self._h, arithmetic)
-        del keep
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            self.lib.dim_lg_destroy(h)
-            self._h = None
-
-    def _stream(self):
-        if self.device.type == "cuda":
-            return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        return None
-
-    def _ctx(self):
-        """The library launches on the CURRENT HIP device: make it the handle's."""
-        import contextlib
-        return torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext()
 
     def match_batch_guarded(self, *a, logger=None, **k):
         """match_batch under the fp16x3 range guard (capi.run_guarded): synchronises."""
-        with self._ctx():
-            return capi.run_guarded(self.lib, self._stream(), lambda: self.match_batch(*a, **k), "LightGlue", self.on_saturation, logger, handle=self._h, arithmetic=self.arithmetic)
+        return self.guarded(lambda: self.match_batch(*a, **k), "LightGlue", logger)
 
     @torch.no_grad()
     def match_batch(self, kpts_tab, desc_tab, n_tab, size_tab, pair_idx=None, n_pairs=None, dense=False, out=None):

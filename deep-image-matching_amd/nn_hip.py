@@ -8,7 +8,6 @@ is no CPU fallback.
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes
 from typing import Optional
 
@@ -25,53 +24,29 @@ def check_mode(mode) -> str:
     return mode
 
 
-class NearestNeighborHIP:
+class NearestNeighborHIP(capi.ResidentHandle):
     """Resident nearest-neighbour descriptor matcher on one GPU (csrc/nn_match.hip)."""
+
+    _destroy = "dim_nn_destroy"
 
     def __init__(self, mode: str = "smnn", th: float = 0.8, dim: int = 256, max_pairs: int = 1, max_kpts: int = 2048, device="cuda",
                  lib=None, on_saturation: str = "fallback", arithmetic=None, f16_exact: bool = False):
         self.mode, self.th, self.input_dim = check_mode(mode), float(th), int(dim)
-        self.arithmetic = arithmetic        # None: the process default; "fp16x3" | "bf16x6" | "fp32": this handle only
-        self.on_saturation = on_saturation  # fp16x3 range guard policy: "fallback" (bf16x6 re-run) | "raise" | "off"
         self.f16_exact = bool(f16_exact)    # default of match_batch's f16_exact: the tables hold float16-exact values (features.h5)
-        self.lib = lib if lib is not None else capi.load()
-        self.device = torch.device(device)
-        if lib is None and capi.installed_device() is None and self.device.type != "cuda":
-            raise capi.DimHipError("NearestNeighborHIP needs a HIP device; there is no CPU fallback")
+        self._open(device, lib, on_saturation, arithmetic)
         capi.declare_nn(self.lib)
         self.max_pairs = int(max_pairs)
-        self._h = ctypes.c_void_p()
         cfg = capi.NnConfig(capi.NN_MODES[self.mode], self.th)
-        with self._ctx():
-            capi.check(self.lib, self.lib.dim_nn_create(ctypes.byref(cfg), self.max_pairs, int(max_kpts), self.input_dim, ctypes.byref(self._h)))
+        self._create(self.lib.dim_nn_create, ctypes.byref(cfg), self.max_pairs, int(max_kpts), self.input_dim)
         self.nk = self.lib.dim_nn_max_kpts(self._h)
-        if arithmetic is not None:
-            capi.set_handle_arithmetic(self.lib, self._h, arithmetic)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            self.lib.dim_nn_destroy(h)
-            self._h = None
 
     def workspace_bytes(self) -> int:
         """Device bytes the handle owns (no M x N buffer among them)."""
         return int(self.lib.dim_nn_workspace_bytes(self._h))
 
-    def _stream(self):
-        if self.device.type == "cuda":
-            return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        return None
-
-    def _ctx(self):
-        """The library launches on the CURRENT HIP device: make it the handle's."""
-        return torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext()
-
     def match_batch_guarded(self, *a, logger=None, **k):
         """match_batch under the fp16x3 range guard (capi.run_guarded): synchronises."""
-        with self._ctx():
-            return capi.run_guarded(self.lib, self._stream(), lambda: self.match_batch(*a, **k), "nearest-neighbour matcher", self.on_saturation, logger,
-                                    handle=self._h, arithmetic=self.arithmetic)
+        return self.guarded(lambda: self.match_batch(*a, **k), "nearest-neighbour matcher", logger)
 
     @torch.no_grad()
     def match_batch(self, kpts_tab, desc_tab, n_tab, size_tab=None, pair_idx=None, n_pairs=None, out=None, taps: bool = False,

@@ -70,9 +70,8 @@ def pairs_from_retrieval(query_names: Sequence[str], db_names: Sequence[str], qu
     sim = torch.empty(nq, nd, dtype=torch.float32, device=dev)
     idx = torch.empty(nq, k, dtype=torch.int32, device=dev)
     val = torch.empty(nq, k, dtype=torch.float32, device=dev)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
-    import contextlib
-    with (torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()):   # launch on dev, not on the current device
+    stream = capi.stream_ptr(dev)
+    with capi.device_ctx(dev):   # launch on dev, not on the current device
         capi.check(lib, lib.dim_op_retrieval_topk(capi.ptr(q), nq, capi.ptr(d), nd, D + pad, capi.ptr(invalid), k,
                                                   ctypes.c_float(0.0 if min_score is None else float(min_score)), int(min_score is not None),
                                                   capi.ptr(sim), capi.ptr(idx), capi.ptr(val), stream))
@@ -95,9 +94,7 @@ class LowresPairSelector:
         self._lg: Optional[LightGlueHIP] = None
 
     def _stream(self):
-        if self.device.type == "cuda":
-            return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        return None
+        return capi.stream_ptr(self.device)
 
     def downsample(self, image: np.ndarray) -> torch.Tensor:
         """pairs_generator.py:141-146: size (w, h), scale = resize_max / max, rounded size, INTER_AREA, /255."""
@@ -148,8 +145,7 @@ class LowresPairSelector:
                 out = self._lg.match_batch(kt, dt, nt, st, pair_idx=pidx, n_pairs=len(chunk), out=out)  # the first chunk is the largest
                 counts[torch.tensor(chunk, device=self.device)] = out["n_matches"][: len(chunk)]
 
-        with self._lg._ctx():
-            capi.run_guarded(self.lib, self._stream(), run, "matching_lowres", self._lg.on_saturation, handle=self._lg._h, arithmetic=self._lg.arithmetic)
+        self._lg.guarded(run, "matching_lowres")
         if self.world > 1:
             import torch.distributed as dist
             dist.all_reduce(counts, op=dist.ReduceOp.SUM)  # shards are disjoint: the sum is the gather

@@ -85,13 +85,7 @@ def _all_gather_cat(t: torch.Tensor, world: int) -> torch.Tensor:
 def _guarded(net, fn, what: str):
     """fn() under the fp16x3 range guard of ``net`` (capi.run_guarded): one counter read-back per phase; a phase that
     left the exact range of the fp16 split is repeated in bf16x6."""
-    from . import capi
-
-    with net._ctx():
-        # the handle and its own arithmetic override (plugin option `arithmetic`): the guard must decide from THAT handle's mode and re-run
-        # THAT handle in bf16x6 — a handle override beats the process default inside the library (ADVICE r5)
-        return capi.run_guarded(net.lib, net._stream(), fn, what, getattr(net, "on_saturation", "fallback"), handle=getattr(net, "_h", None),
-                                arithmetic=getattr(net, "arithmetic", None))
+    return net.guarded(fn, what)
 
 
 class PairMatchingPipeline:
@@ -156,7 +150,6 @@ class PairMatchingPipeline:
         Returns, on every rank, (n_matches [P], matches [P,NK,2] int64, scores [P,NK]) in the
         order of ``pairs``; with ``aux`` additionally (stop [P] int32, prune01 [P,2,NK] int32) — the reference's
         "stop" / "prune0" / "prune1" outputs (LGN:570-577), gathered the same way (parity tests)."""
-        import ctypes
         import time
         from . import capi
         kp, sc, de, n, size = table
@@ -179,7 +172,7 @@ class PairMatchingPipeline:
         cnt, stp, rows = flat[o[0]:o[1]], flat[o[1]:o[2]], flat[o[2]:o[3]].view(per, NK, 3)
         prn = flat[o[3]:o[4]].view(per, 2, NK) if aux else None
         my_pairs = pairs[mine].to(dev, torch.int32).contiguous()
-        stream = (lambda: ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)) if dev.type == "cuda" else (lambda: None)
+        stream = lambda: capi.stream_ptr(dev)
         t0 = time.perf_counter()
 
         def run():
@@ -461,7 +454,7 @@ class TiledPairPipeline:
                 for s, v in enumerate(views):
                     votes[s, : v.shape[0], : v.shape[1]] = v
 
-            stream = ctypes_stream_of(dev)
+            stream = capi.stream_ptr(dev)
             capi.run_guarded(pre.lib, stream, run, "tile preselection", "fallback")       # one guard read (and synchronisation) for the phase
             vh = votes.cpu().numpy().astype(np.int64)
             for s, p in enumerate(mine):
@@ -584,7 +577,7 @@ class TiledPairPipeline:
         pidx_all = torch.tensor([[r0, r1] for _, r0, r1 in tp], dtype=torch.int32, device=dev).contiguous()
         slot_all = torch.tensor([s for s, _, _ in tp], dtype=torch.int32, device=dev)
         keys = torch.empty(len(tp), NK, dtype=torch.int64, device=dev)
-        stream = ctypes_stream_of(dev)
+        stream = capi.stream_ptr(dev)
 
         def run():
             out = None
@@ -614,11 +607,6 @@ def np_shape(image):
 def np_f32(x):
     import numpy as np
     return np.asarray(x, dtype=np.float32).reshape(2)
-
-
-def ctypes_stream_of(dev):
-    import ctypes
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if torch.device(dev).type == "cuda" else None
 
 
 def _band1(image):

@@ -359,7 +359,92 @@ def featuresDict2Lightglue(feats: dict) -> dict:
     return out
 
 
-class LightGlueMatcher(BatchedTileMatchingMixin, _MatcherBase):
+class _ResidentMatcherMixin:
+    """What LightGlueMatcher and KorniaMatcher share: the resize policy of their two resident handles (``_net``: one pair per call, ``_net_b``:
+    batched) and the one-pair hand-over through raw staging.  The matcher supplies ``_new_net(pairs, n)`` and, where a handle can go stale
+    for another reason than its size, ``_stale(net)``."""
+
+    def _stale(self, net) -> bool:
+        return False
+
+    def _dev(self):
+        return self._device if isinstance(self._device, (str, torch.device)) else "cuda"
+
+    def _ensure(self, n: int):
+        if self._net is None or n > self._net_n or self._stale(self._net):
+            # a handle is rebuilt when a pair has more keypoints than it holds (LightGlue ~0.5 - 1 s: weight splitting, uploads, allocations).  Since round 6 an
+            # oversized handle costs nothing measurable (launch shapes follow the pair, not the handle: 2048 keypoints on a 4096 / 8192-row handle 1.464 / 1.485 vs
+            # 1.461 ms, scripts/gpu_lg_capacity_cost.py) and a 4096-row handle is ~0.2 GB (the NN matcher's O(n^2 / 128) bytes), so on a GPU the first one already
+            # holds 4096 keypoints per image
+            floor = 4096 if str(getattr(self._dev(), "type", self._dev())).startswith("cuda") else 256
+            self._net_n = max(floor, 1 << (max(n, 1) - 1).bit_length())
+            self._net = self._new_net(1, self._net_n)
+
+    def _ensure_pairs(self, n: int, pairs: int):
+        """Batched instance (BatchedImageMatcher.match_pairs, tile_matching.BatchedTileMatchingMixin)."""
+        cur = getattr(self, "_net_b", None)
+        if cur is None or n > self._net_b_n or pairs > self._net_b_p or self._stale(cur):
+            self._net_b_n = max(256, 1 << (max(n, 1) - 1).bit_length(), getattr(self, "_net_b_n", 0))
+            self._net_b_p = max(pairs, getattr(self, "_net_b_p", 0))
+            self._net_b = self._new_net(self._net_b_p, self._net_b_n)
+        return self._net_b
+
+    def _match_one_pair(self, tag: str, what: str, header, arrays, describe, cap: int, D: int, raw_floor: int, extra_out, match) -> np.ndarray:
+        """One pair on ``self._net`` with ONE host-to-device and ONE device-to-host transfer.  ``header``: (byte offset, array) words of the first 256
+        staging bytes; ``arrays``: the raw arrays, each at the next 256-byte boundary behind it; ``describe(base, offs)``: the two LgRawFeatures of
+        dim_lg_stage_features, which builds the fp32 (N, D) feature table on the device; ``raw_floor``: bytes of device staging a handle-sized pair
+        needs; ``extra_out(NK, dev)``: the matcher's output tensors besides the flat [n_matches (int32) | pad | matches NK x 2] buffer that comes
+        back; ``match(kt, dt, rawd, out)``: the match_batch call.  The buffers live on a GPU in page-locked memory (``_staging``) and on the device in
+        ``_lean``, rebuilt when the handle changed or a pair outgrew them.  Returns the (S, 2) int64 index pairs."""
+        net = self._net
+        dev = torch.device(net.device)
+        on_gpu = dev.type == "cuda"
+        NK = net.nk
+        offs, cur = [], 256
+        for arr in arrays:
+            offs.append(cur)
+            cur += (arr.nbytes + 255) & ~255
+        nbytes_out = (2 + NK * 2) * 8
+        if on_gpu:
+            st = self.__dict__.setdefault("_staging", _PinnedStaging())
+            pin, pout = st.get(tag + "_in", cur)[:cur], st.get(tag + "_out", nbytes_out)[:nbytes_out]
+        else:
+            pin, pout = torch.empty(cur, dtype=torch.uint8), torch.empty(nbytes_out, dtype=torch.uint8)
+        pout = pout.view(torch.int64)
+        h = pin.numpy()
+        for o, words in header:
+            h[o:o + words.nbytes] = words.view(np.uint8)
+        for arr, o in zip(arrays, offs):
+            if arr.nbytes:
+                h[o:o + arr.nbytes] = arr.reshape(-1).view(np.uint8)
+        lean = self.__dict__.get("_lean")
+        tab_floats = 2 * cap * (2 + D)
+        if lean is None or lean["net"] is not net or lean["raw"].numel() < cur or lean["tab"].numel() < tab_floats:
+            flat = torch.zeros(2 + NK * 2, dtype=torch.int64, device=dev)
+            out = {"matches": flat[2:].view(1, NK, 2), "scores": torch.zeros(1, NK, dtype=torch.float32, device=dev),
+                   "n_matches": flat[:1].view(torch.int32)[:1], **extra_out(NK, dev)}
+            lean = {"net": net, "raw": torch.empty(max(cur, raw_floor), dtype=torch.uint8, device=dev),
+                    "tab": torch.empty(max(tab_floats, 2 * NK * (2 + D)), dtype=torch.float32, device=dev), "flat": flat, "out": out}
+            self.__dict__["_lean"] = lean
+        rawd, tab = lean["raw"], lean["tab"]
+        descr = describe(rawd.data_ptr(), offs)
+        kt, dt = tab[: 4 * cap].view(2, cap, 2), tab[4 * cap: 4 * cap + 2 * cap * D].view(2, cap, D)
+
+        def run():
+            rawd[:cur].copy_(pin, non_blocking=True)
+            capi.check(net.lib, net.lib.dim_lg_stage_features(ctypes.byref(descr[0]), ctypes.byref(descr[1]), int(cap), int(D), capi.ptr(kt), capi.ptr(dt), net._stream()))
+            match(kt, dt, rawd, lean["out"])
+            pout.copy_(lean["flat"], non_blocking=True)   # enqueued behind the match: the range guard's synchronisation covers it
+
+        net.guarded(run, what, logger)
+        if on_gpu:
+            torch.cuda.current_stream(dev).synchronize()
+        res = pout.numpy()
+        S = int(res[:1].view(np.int32)[0])
+        return res[2:2 + 2 * S].reshape(S, 2).copy()
+
+
+class LightGlueMatcher(_ResidentMatcherMixin, BatchedTileMatchingMixin, _MatcherBase):
     """matchers/lightglue.py:77 — LightGlue on the gfx950 library."""
 
     _default_conf = {
@@ -404,27 +489,8 @@ class LightGlueMatcher(BatchedTileMatchingMixin, _MatcherBase):
         if self._localfeatures == "disk":
             self.max_feat_no_tiling = 50000
 
-    def _ensure(self, n: int):
-        if self._net is None or n > self._net_n:
-            dev = self._device if isinstance(self._device, (str, torch.device)) else "cuda"
-            # a handle is rebuilt when a pair has more keypoints than it holds (~0.5 - 1 s: weight splitting, uploads, allocations).  Since round 6 an oversized
-            # handle costs nothing measurable (launch shapes follow the pair, not the handle: 2048 keypoints on a 4096 / 8192-row handle 1.464 / 1.485 vs 1.461 ms,
-            # scripts/gpu_lg_capacity_cost.py) and a 4096-row handle is ~0.2 GB, so on a GPU the first one already holds 4096 keypoints per image
-            floor = 4096 if str(getattr(dev, "type", dev)).startswith("cuda") else 256
-            self._net_n = max(floor, 1 << (max(n, 1) - 1).bit_length())
-            self._net = LightGlueHIP(self._sd, self._conf, max_pairs=1, max_kpts=self._net_n, device=dev, lib=self._lib,
-                                     on_saturation=self._on_sat, arithmetic=self._arith)
-
-    def _ensure_pairs(self, n: int, pairs: int):
-        """Batched instance for tile-pair matching (tile_matching.BatchedTileMatchingMixin)."""
-        cur = getattr(self, "_net_b", None)
-        if cur is None or n > self._net_b_n or pairs > self._net_b_p:
-            self._net_b_n = max(256, 1 << (max(n, 1) - 1).bit_length(), getattr(self, "_net_b_n", 0))
-            self._net_b_p = max(pairs, getattr(self, "_net_b_p", 0))
-            dev = self._device if isinstance(self._device, (str, torch.device)) else "cuda"
-            self._net_b = LightGlueHIP(self._sd, self._conf, max_pairs=self._net_b_p, max_kpts=self._net_b_n, device=dev, lib=self._lib,
-                                       on_saturation=self._on_sat, arithmetic=self._arith)
-        return self._net_b
+    def _new_net(self, pairs: int, n: int) -> LightGlueHIP:
+        return LightGlueHIP(self._sd, self._conf, max_pairs=pairs, max_kpts=n, device=self._dev(), lib=self._lib, on_saturation=self._on_sat, arithmetic=self._arith)
 
     @torch.no_grad()
     def _match_pairs(self, feats0: dict, feats1: dict) -> np.ndarray:
@@ -486,56 +552,20 @@ class LightGlueMatcher(BatchedTileMatchingMixin, _MatcherBase):
         m, n = k0.shape[0], k1.shape[0]
         if (m and (d0.shape[0] if dn0 else d0.shape[1]) != D) or (n and (d1.shape[0] if dn1 else d1.shape[1]) != D):
             raise ValueError(f"descriptor dimension {d0.shape} / {d1.shape} does not match the matcher's input_dim {D}")
-        cap = max(m, n, 1)
-        # raw staging: [sizes 4 f32 | counts 2 i32 | pad] then the four arrays at 256-byte boundaries
-        offs, cur = [], 256
-        for arr in (k0, d0, k1, d1):
-            offs.append(cur)
-            cur += (arr.nbytes + 255) & ~255
-        st = self.__dict__.setdefault("_staging", _PinnedStaging())
-        pin = st.get("lg_in", cur)[:cur]
-        h = pin.numpy()
-        h[:16].view(np.float32)[0:2] = size_of(f0, k0)
-        h[:16].view(np.float32)[2:4] = size_of(f1, k1)
-        h[16:24].view(np.int32)[:] = (m, n)
-        for arr, o in zip((k0, d0, k1, d1), offs):
-            if arr.nbytes:
-                h[o:o + arr.nbytes] = arr.reshape(-1).view(np.uint8)
-        lean = self.__dict__.get("_lean")
         NK = net.nk
-        tab_floats = 2 * cap * (2 + D)
-        if lean is None or lean["net"] is not net or lean["raw"].numel() < cur or lean["tab"].numel() < tab_floats:
-            flat = torch.zeros(2 + NK * 2, dtype=torch.int64, device=dev)       # [n_matches (int32) | pad | matches NK x 2]
-            out = {"matches": flat[2:].view(1, NK, 2), "scores": torch.zeros(1, NK, dtype=torch.float32, device=dev),
-                   "n_matches": flat[:1].view(torch.int32)[:1], "matches01": torch.zeros(1, 2, NK, dtype=torch.int32, device=dev),
-                   "mscores01": torch.zeros(1, 2, NK, dtype=torch.float32, device=dev), "stop": torch.zeros(1, dtype=torch.int32, device=dev),
-                   "prune01": torch.zeros(1, 2, NK, dtype=torch.int32, device=dev)}
-            lean = {"net": net, "raw": torch.empty(max(cur, 256 + 4 * 2 * NK * (2 + D) + 1024), dtype=torch.uint8, device=dev),
-                    "tab": torch.empty(max(tab_floats, 2 * NK * (2 + D)), dtype=torch.float32, device=dev), "flat": flat, "out": out}
-            self.__dict__["_lean"] = lean
-        rawd, tab = lean["raw"], lean["tab"]
-        pout = st.get("lg_out", (2 + NK * 2) * 8)[: (2 + NK * 2) * 8].view(torch.int64)
-        base = rawd.data_ptr()
-        descr = [capi.LgRawFeatures(base + offs[0], base + offs[1], m, int(k0.dtype == np.float16), int(d0.dtype == np.float16), dn0),
-                 capi.LgRawFeatures(base + offs[2], base + offs[3], n, int(k1.dtype == np.float16), int(d1.dtype == np.float16), dn1)]
-        kt, dt = tab[: 4 * cap].view(2, cap, 2), tab[4 * cap: 4 * cap + 2 * cap * D].view(2, cap, D)
-        sizes, counts = rawd[:16].view(torch.float32).view(2, 2), rawd[16:24].view(torch.int32)
-
-        def run():
-            rawd[:cur].copy_(pin, non_blocking=True)
-            capi.check(net.lib, net.lib.dim_lg_stage_features(ctypes.byref(descr[0]), ctypes.byref(descr[1]), int(cap), int(D), capi.ptr(kt), capi.ptr(dt), net._stream()))
-            net.match_batch(kt, dt, counts, sizes, n_pairs=1, out=lean["out"])
-            pout.copy_(lean["flat"], non_blocking=True)
-
-        with net._ctx():
-            capi.run_guarded(net.lib, net._stream(), run, "LightGlue", net.on_saturation, logger, handle=net._h, arithmetic=net.arithmetic)
-        torch.cuda.current_stream(dev).synchronize()
-        res = pout.numpy()
-        S = int(res[:1].view(np.int32)[0])
-        return res[2:2 + 2 * S].reshape(S, 2).copy()
+        f16 = lambda a: int(a.dtype == np.float16)
+        return self._match_one_pair(
+            "lg", "LightGlue",
+            [(0, np.concatenate([size_of(f0, k0), size_of(f1, k1)]).astype(np.float32)), (16, np.array((m, n), dtype=np.int32))],   # [sizes 4 f32 | counts 2 i32 | pad]
+            (k0, d0, k1, d1),
+            lambda base, offs: [capi.LgRawFeatures(base + offs[0], base + offs[1], m, f16(k0), f16(d0), dn0), capi.LgRawFeatures(base + offs[2], base + offs[3], n, f16(k1), f16(d1), dn1)],
+            max(m, n, 1), D, 256 + 4 * 2 * NK * (2 + D) + 1024,
+            lambda NK, dev: {"matches01": torch.zeros(1, 2, NK, dtype=torch.int32, device=dev), "mscores01": torch.zeros(1, 2, NK, dtype=torch.float32, device=dev),
+                             "stop": torch.zeros(1, dtype=torch.int32, device=dev), "prune01": torch.zeros(1, 2, NK, dtype=torch.int32, device=dev)},
+            lambda kt, dt, rawd, out: net.match_batch(kt, dt, rawd[16:24].view(torch.int32), rawd[:16].view(torch.float32).view(2, 2), n_pairs=1, out=out))
 
 
-class KorniaMatcher(BatchedTileMatchingMixin, _MatcherBase):
+class KorniaMatcher(_ResidentMatcherMixin, BatchedTileMatchingMixin, _MatcherBase):
     """matchers/kornia_matcher.py:9 — kornia.feature.DescriptorMatcher(match_mode, th) on the gfx950 library (csrc/nn_match.hip): the matcher of the
     shipped ``superpoint+kornia_matcher`` pipeline and of the SIFT / KeyNet / DeDoDe pipelines.  match_mode nn / mnn / snn / smnn; kornia's other
     modes (fginn, adalam, lightglue) are rejected here, at construction.  The match list is always idx0-ascending (kornia's mnn lists by idx1 when
@@ -566,25 +596,11 @@ class KorniaMatcher(BatchedTileMatchingMixin, _MatcherBase):
         self._dim = int(dim)
 
     def _new_net(self, pairs: int, n: int) -> NearestNeighborHIP:
-        dev = self._device if isinstance(self._device, (str, torch.device)) else "cuda"
-        return NearestNeighborHIP(self._mode, self._th, dim=self._dim, max_pairs=pairs, max_kpts=n, device=dev, lib=self._lib,
+        return NearestNeighborHIP(self._mode, self._th, dim=self._dim, max_pairs=pairs, max_kpts=n, device=self._dev(), lib=self._lib,
                                   on_saturation=self._on_sat, arithmetic=self._arith)
 
-    def _ensure(self, n: int):
-        if self._net is None or n > self._net_n or self._net.input_dim != self._dim:
-            # launch shapes follow the pair, not the handle, and a handle owns O(n^2 / 128) bytes: on a GPU the first one already holds 4096 rows
-            floor = 4096 if str(getattr(self._device, "type", self._device)).startswith("cuda") else 256
-            self._net_n = max(floor, 1 << (max(n, 1) - 1).bit_length())
-            self._net = self._new_net(1, self._net_n)
-
-    def _ensure_pairs(self, n: int, pairs: int):
-        """Batched instance (BatchedImageMatcher.match_pairs, tile_matching.BatchedTileMatchingMixin)."""
-        cur = getattr(self, "_net_b", None)
-        if cur is None or n > self._net_b_n or pairs > self._net_b_p or cur.input_dim != self._dim:
-            self._net_b_n = max(256, 1 << (max(n, 1) - 1).bit_length(), getattr(self, "_net_b_n", 0))
-            self._net_b_p = max(pairs, getattr(self, "_net_b_p", 0))
-            self._net_b = self._new_net(self._net_b_p, self._net_b_n)
-        return self._net_b
+    def _stale(self, net) -> bool:
+        return net.input_dim != self._dim   # the handle is built for one descriptor width
 
     @torch.no_grad()
     def _match_pairs(self, feats0: dict, feats1: dict) -> np.ndarray:
@@ -609,50 +625,12 @@ class KorniaMatcher(BatchedTileMatchingMixin, _MatcherBase):
         D = D0
         self._set_dim(D)
         self._ensure(max(m, n))
-        net = self._net
-        dev = torch.device(net.device)
-        on_gpu = dev.type == "cuda"
-        cap, NK = max(m, n, 1), net.nk
-        offs, cur = [], 256                    # raw staging: [counts 2 i32 | pad] then the two arrays at 256-byte boundaries
-        for arr in (d0, d1):
-            offs.append(cur)
-            cur += (arr.nbytes + 255) & ~255
-        st = self.__dict__.setdefault("_staging", _PinnedStaging())
-        pin = st.get("nn_in", cur)[:cur] if on_gpu else torch.empty(cur, dtype=torch.uint8)
-        h = pin.numpy()
-        h[:8].view(np.int32)[:] = (m, n)
-        for arr, o in zip((d0, d1), offs):
-            if arr.nbytes:
-                h[o:o + arr.nbytes] = arr.reshape(-1).view(np.uint8)
-        lean = self.__dict__.get("_lean")
-        tab_floats = 2 * cap * (2 + D)
-        if lean is None or lean["net"] is not net or lean["raw"].numel() < cur or lean["tab"].numel() < tab_floats:
-            flat = torch.zeros(2 + NK * 2, dtype=torch.int64, device=dev)       # [n_matches (int32) | pad | matches NK x 2]
-            out = {"matches": flat[2:].view(1, NK, 2), "scores": torch.zeros(1, NK, dtype=torch.float32, device=dev), "n_matches": flat[:1].view(torch.int32)[:1]}
-            lean = {"net": net, "raw": torch.empty(max(cur, 256 + 4 * 2 * NK * D + 1024), dtype=torch.uint8, device=dev),
-                    "tab": torch.empty(max(tab_floats, 2 * NK * (2 + D)), dtype=torch.float32, device=dev), "flat": flat, "out": out}
-            self.__dict__["_lean"] = lean
-        rawd, tab = lean["raw"], lean["tab"]
-        nbytes_out = (2 + NK * 2) * 8
-        pout = (st.get("nn_out", nbytes_out)[:nbytes_out] if on_gpu else torch.empty(nbytes_out, dtype=torch.uint8)).view(torch.int64)
-        base = rawd.data_ptr()
+        net, NK = self._net, self._net.nk
         f16 = [int(d0.dtype == np.float16), int(d1.dtype == np.float16)]
-        # the staging kernel converts keypoints too; this matcher has none to give it: it reads the first 2 n descriptor values as stand-ins (into kt, unused)
-        descr = [capi.LgRawFeatures(base + offs[0], base + offs[0], m, f16[0], f16[0], dn0), capi.LgRawFeatures(base + offs[1], base + offs[1], n, f16[1], f16[1], dn1)]
-        kt, dt = tab[: 4 * cap].view(2, cap, 2), tab[4 * cap: 4 * cap + 2 * cap * D].view(2, cap, D)
-        counts = rawd[:8].view(torch.int32)
         exact = bool(f16[0] and f16[1])      # float16 inputs: every table value has a zero low piece (one MFMA term instead of three, same bits)
-
-        def run():
-            rawd[:cur].copy_(pin, non_blocking=True)
-            capi.check(net.lib, net.lib.dim_lg_stage_features(ctypes.byref(descr[0]), ctypes.byref(descr[1]), int(cap), int(D), capi.ptr(kt), capi.ptr(dt), net._stream()))
-            net.match_batch(None, dt, counts, None, n_pairs=1, out=lean["out"], f16_exact=exact)
-            pout.copy_(lean["flat"], non_blocking=True)
-
-        with net._ctx():
-            capi.run_guarded(net.lib, net._stream(), run, "KorniaMatcher", net.on_saturation, logger, handle=net._h, arithmetic=net.arithmetic)
-        if on_gpu:
-            torch.cuda.current_stream(dev).synchronize()
-        res = pout.numpy()
-        S = int(res[:1].view(np.int32)[0])
-        return res[2:2 + 2 * S].reshape(S, 2).copy()
+        return self._match_one_pair(
+            "nn", "KorniaMatcher", [(0, np.array((m, n), dtype=np.int32))], (d0, d1),                                       # [counts 2 i32 | pad]
+            # the staging kernel converts keypoints too; this matcher has none to give it: it reads the first 2 n descriptor values as stand-ins (into kt, unused)
+            lambda base, offs: [capi.LgRawFeatures(base + offs[0], base + offs[0], m, f16[0], f16[0], dn0), capi.LgRawFeatures(base + offs[1], base + offs[1], n, f16[1], f16[1], dn1)],
+            max(m, n, 1), D, 256 + 4 * 2 * NK * D + 1024, lambda NK, dev: {},
+            lambda kt, dt, rawd, out: net.match_batch(None, dt, rawd[:8].view(torch.int32), None, n_pairs=1, out=out, f16_exact=exact))

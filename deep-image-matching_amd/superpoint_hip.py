@@ -30,58 +30,29 @@ class _SpConfig(ctypes.Structure):
     ]
 
 
-class SuperPointHIP:
+class SuperPointHIP(capi.ResidentHandle):
     """Resident SuperPoint on one GPU.  cfg keys follow SPN:112-118 (+ fix_sampling)."""
 
+    _destroy = "dim_sp_destroy"
     default_config = {"nms_radius": 4, "keypoint_threshold": 0.005, "max_keypoints": -1, "remove_borders": 4,
                       "fix_sampling": False}
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: Optional[dict] = None, max_batch: int = 1,
                  max_hw=(1024, 1024), capacity: Optional[int] = None, device="cuda", lib=None, on_saturation: str = "fallback", arithmetic=None):
         self.cfg = {**self.default_config, **(cfg or {})}
-        self.arithmetic = arithmetic        # None: the process default (capi.set_arithmetic); "fp16x3" | "bf16x6" | "fp32": this handle only
-        self.on_saturation = on_saturation  # fp16x3 range guard policy of __call__: "fallback" (bf16x6 re-run) | "raise" | "off"
         mk = self.cfg["max_keypoints"]
         if mk == 0 or mk < -1:
             raise ValueError('"max_keypoints" must be positive or "-1"')  # SPN:152-154
-        self.lib = lib if lib is not None else capi.load()
-        self.device = torch.device(device)
-        if lib is None and self.device.type != "cuda":
-            raise capi.DimHipError("SuperPointHIP needs a HIP device; there is no CPU fallback")
+        self._open(device, lib, on_saturation, arithmetic)
         self.max_batch, self.max_hw = int(max_batch), (int(max_hw[0]), int(max_hw[1]))
         self.capacity = int(capacity if capacity is not None else (mk if mk > 0 else 8192))
         w = _SpWeights()
-        keep = []
         for i, (name, *_ ) in enumerate(SP_LAYERS):
-            wt = state_dict[name + ".weight"].detach().float().contiguous().cpu()
-            bt = state_dict[name + ".bias"].detach().float().contiguous().cpu()
-            keep += [wt, bt]
-            w.conv_w[i] = wt.data_ptr()
-            w.conv_b[i] = bt.data_ptr()
+            w.conv_w[i] = self._host(state_dict[name + ".weight"])
+            w.conv_b[i] = self._host(state_dict[name + ".bias"])
         c = _SpConfig(int(self.cfg["nms_radius"]), float(self.cfg["keypoint_threshold"]), int(mk),
                       int(self.cfg["remove_borders"]), int(bool(self.cfg["fix_sampling"])))
-        self._h = ctypes.c_void_p()
-        with self._ctx():
-            capi.check(self.lib, self.lib.dim_sp_create(ctypes.byref(w), ctypes.byref(c), self.max_batch, self.max_hw[0],
-                                                        self.max_hw[1], self.capacity, ctypes.byref(self._h)))
-        if arithmetic is not None:
-            capi.set_handle_arithmetic(self.lib, self._h, arithmetic)
-        del keep
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            self.lib.dim_sp_destroy(h)
-            self._h = None
-
-    def _stream(self):
-        if self.device.type == "cuda":
-            return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        return None
-
-    def _ctx(self):
-        """The library launches on the CURRENT HIP device: make it the handle's."""
-        return torch.cuda.device(self.device) if self.device.type == "cuda" else _null()
+        self._create(self.lib.dim_sp_create, ctypes.byref(w), ctypes.byref(c), self.max_batch, self.max_hw[0], self.max_hw[1], self.capacity)
 
     def candidate_counts(self, batch: int) -> torch.Tensor:
         """NMS survivors above threshold / border per image of the last call, BEFORE top-k / the capacity
@@ -121,9 +92,7 @@ class SuperPointHIP:
 
     def extract_batch_guarded(self, images: torch.Tensor, out=None, logger=None):
         """extract_batch under the fp16x3 range guard (capi.run_guarded): synchronises."""
-        with self._ctx():
-            return capi.run_guarded(self.lib, self._stream(), lambda: self.extract_batch(images, out=out), "SuperPoint",
-                                    self.on_saturation, logger, handle=self._h, arithmetic=self.arithmetic)
+        return self.guarded(lambda: self.extract_batch(images, out=out), "SuperPoint", logger)
 
     @torch.no_grad()
     def __call__(self, image: torch.Tensor) -> dict:
@@ -145,36 +114,11 @@ class SuperPointHIP:
                   "nms_map": (batch, H8, W8), "dense_desc": (batch, h, w, 256)}
         out = {}
         for (name, shape), p in zip(shapes.items(), ptrs):
-            out[name] = _copy_from(self.lib, p.value, shape, self.device)
+            out[name] = capi.copy_from_device(self.lib, p.value, shape, self.device)
         return out
-
 
     def debug_conv1b(self, batch: int, H: int, W: int) -> torch.Tensor:
         """conv1b's pooled output of the last call as a CPU tensor [batch, H/2, W/2, 64] (fp32 NHWC): dim_sp_debug_conv1b."""
         p, h2, w2 = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
         capi.check(self.lib, self.lib.dim_sp_debug_conv1b(self._h, int(batch), int(H), int(W), ctypes.byref(p), ctypes.byref(h2), ctypes.byref(w2)))
-        return _copy_from(self.lib, p.value, (batch, h2.value, w2.value, 64), self.device)
-
-
-class _null:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
-def _copy_from(lib, addr: int, shape, device) -> torch.Tensor:
-    """Copy a raw device buffer into a CPU tensor (hipMemcpy through torch)."""
-    import math
-
-    n = math.prod(shape)
-    if device.type == "cuda":
-        torch.cuda.synchronize(device)
-        out = torch.empty(n, dtype=torch.float32, device=device)
-        rc = ctypes.CDLL("libamdhip64.so").hipMemcpy(ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(addr), ctypes.c_size_t(n * 4), 3)
-        if rc != 0:
-            raise capi.DimHipError(f"hipMemcpy failed: {rc}")
-        return out.cpu().reshape(shape)
-    buf = (ctypes.c_float * n).from_address(addr)
-    return torch.frombuffer(buf, dtype=torch.float32).clone().reshape(shape)
+        return capi.copy_from_device(self.lib, p.value, (batch, h2.value, w2.value, 64), self.device)

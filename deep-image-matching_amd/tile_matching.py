@@ -255,7 +255,7 @@ class TilePreselector:
         self._cache_size = cache_size
 
     def _stream(self):
-        return ctypes_stream(self.device)
+        return capi.stream_ptr(self.device)
 
     @staticmethod
     def _capacity() -> int:
@@ -399,12 +399,6 @@ class TilePreselector:
         return kp0.astype(np.float32), kp1.astype(np.float32)
 
 
-def ctypes_stream(device):
-    if torch.device(device).type == "cuda":
-        return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    return None
-
-
 def ctypes_float(x):
     return ctypes.c_float(float(np.float32(x)))
 
@@ -464,11 +458,6 @@ def match_tile_pairs_batched(net_for, features0: dict, features1: dict, tile_pai
     return full
 
 
-def _stream_of(dev):
-    import ctypes
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if torch.device(dev).type == "cuda" else None
-
-
 def _row_stride(t: torch.Tensor) -> int:
     return int(t.stride(0)) if t.shape[0] > 1 else max(1, int(t.shape[1]) if t.dim() > 1 else 1)
 
@@ -478,7 +467,7 @@ def device_tile_counts(lib, f: dict, n_tiles: int) -> torch.Tensor:
     from . import capi
     ti = f["tile_idx"]
     counts = torch.empty(n_tiles, dtype=torch.int32, device=ti.device)
-    capi.check(lib, lib.dim_op_tile_counts(capi.ptr(ti), _row_stride(ti), int(ti.numel()), n_tiles, capi.ptr(counts), _stream_of(ti.device)))
+    capi.check(lib, lib.dim_op_tile_counts(capi.ptr(ti), _row_stride(ti), int(ti.numel()), n_tiles, capi.ptr(counts), capi.stream_ptr(ti.device)))
     return counts
 
 
@@ -497,7 +486,7 @@ def device_group_by_tile(lib, f: dict, row_of_tile: torch.Tensor, cap: int, kt, 
     kp, de = f["keypoints"], f["descriptors_nd"]      # (views of one packed [N][4 + D] table in the tiled pipeline: passed with their row strides, not copied)
     assert kp.stride(-1) == 1 and de.stride(-1) == 1 and ti.dtype == kp.dtype == de.dtype == torch.float32
     capi.check(lib, lib.dim_op_group_by_tile(capi.ptr(ti), _row_stride(ti), capi.ptr(kp), _row_stride(kp), capi.ptr(de), _row_stride(de), n, D, capi.ptr(row_of_tile), T,
-                                             int(cap), capi.ptr(kt), capi.ptr(dt), capi.ptr(it), capi.ptr(nt), capi.ptr(ws), _stream_of(ti.device)))
+                                             int(cap), capi.ptr(kt), capi.ptr(dt), capi.ptr(it), capi.ptr(nt), capi.ptr(ws), capi.stream_ptr(ti.device)))
 
 
 def device_unique_match_rows(lib, keys: torch.Tensor, n_slots: int, cap_m: int, rows: torch.Tensor, cnt: torch.Tensor, n_full: Optional[torch.Tensor] = None):
@@ -509,7 +498,7 @@ def device_unique_match_rows(lib, keys: torch.Tensor, n_slots: int, cap_m: int, 
     lib.dim_op_unique_match_rows_workspace_bytes.restype = ctypes.c_size_t
     ws = torch.empty(int(lib.dim_op_unique_match_rows_workspace_bytes(ctypes.c_longlong(n))), dtype=torch.uint8, device=keys.device)
     capi.check(lib, lib.dim_op_unique_match_rows(capi.ptr(keys), ctypes.c_longlong(n), int(n_slots), int(cap_m), int(rows.dtype == torch.int64), capi.ptr(rows),
-                                                 capi.ptr(cnt), capi.ptr(n_full) if n_full is not None else None, capi.ptr(ws), _stream_of(keys.device)))
+                                                 capi.ptr(cnt), capi.ptr(n_full) if n_full is not None else None, capi.ptr(ws), capi.stream_ptr(keys.device)))
 
 
 def match_tile_pairs_batched_device(net_for, f0: dict, f1: dict, tile_pairs: Sequence[Tuple[int, int]], pair_batch: int = 8,
@@ -564,7 +553,7 @@ def match_tile_pairs_batched_device(net_for, f0: dict, f1: dict, tile_pairs: Seq
         pidx = torch.tensor([[row0[a], row1[b]] for a, b in chunk], dtype=torch.int32, device=dev).contiguous()
         o = net.match_batch_guarded(kt, dt, nt, st, pair_idx=pidx, n_pairs=len(chunk), logger=logger)
         capi.check(lib, lib.dim_op_tile_match_keys(capi.ptr(o["matches"]), capi.ptr(o["n_matches"]), capi.ptr(it), capi.ptr(pidx), capi.ptr(zero_slot), len(chunk), NK, cap,
-                                                   capi.ptr(keys[s:s + len(chunk)]), _stream_of(dev)))
+                                                   capi.ptr(keys[s:s + len(chunk)]), capi.stream_ptr(dev)))
     cap_m = len(tile_pairs) * NK
     rows = torch.empty(1, cap_m, 2, dtype=torch.int64, device=dev)
     cnt = torch.zeros(1, dtype=torch.int32, device=dev)

@@ -180,9 +180,8 @@ class BatchedTilingMixin:
         idxs = sorted(origins)
         tables = []
         from . import capi
-        import ctypes
         lib = net.lib
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+        stream = capi.stream_ptr(dev)
         for s in range(0, len(idxs), self.tile_batch):
             chunk = idxs[s:s + self.tile_batch]
             # dim_op_gather_tiles_f32: zero padding, tile slicing and _frame2tensor's / 255 in one pass from the image as it arrived

@@ -45,9 +45,7 @@ class DeviceVerifier:
         self._scratch: Optional[torch.Tensor] = None
 
     def _stream(self):
-        if self.device.type == "cuda":
-            return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        return None
+        return capi.stream_ptr(self.device)
 
     @torch.no_grad()
     def verify_batch(self, kpts_tab: torch.Tensor, matches: torch.Tensor, n_matches: torch.Tensor, pair_idx: Optional[torch.Tensor] = None,

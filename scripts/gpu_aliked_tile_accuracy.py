@@ -28,9 +28,7 @@ def main():
     out = {k: v.cpu() for k, v in net(img).items()}
     taps = net.debug_taps()
     capi = importlib.import_module("deep-image-matching_amd.capi")
-    from importlib import import_module
-    sp = import_module("deep-image-matching_amd.superpoint_hip")
-    score_dev = sp._copy_from(net.lib, taps["score_ptr"], (1, T, T), net.device)[0].cpu()
+    score_dev = capi.copy_from_device(net.lib, taps["score_ptr"], (1, T, T), net.device)[0].cpu()
     r32 = aliked_ref.aliked_forward(img, sd, cfg, taps=True)
     sd64 = {k: v.double() for k, v in sd.items()}
     r64 = aliked_ref.aliked_forward(img.double(), sd64, cfg, taps=True)
