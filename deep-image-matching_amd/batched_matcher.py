@@ -179,10 +179,6 @@ class BatchedImageMatcher:
             self.mat._set_dim(D)
         net = self.mat._ensure_pairs(cap, self.pair_batch)
         dev = net.device
-        if self._verifier is not None and net.nk > 4096:
-            # dim_gv_fundamental stages a pair's correspondences in LDS: at most 4096 matches per pair
-            raise ValueError(f"device verification handles at most 4096 keypoints per image (this run needs {net.nk}); lower "
-                             "max_keypoints, or construct BatchedImageMatcher(verify=False) and verify with verify.HostVerifierPool")
         kt_d, dt_d, nt_d, st_d = (torch.from_numpy(a).to(dev) for a in (kt, dt, nt, st))
         for s in range(0, len(pairs), self.pair_batch):
             chunk = [(Path(a).name, Path(b).name) for a, b in pairs[s:s + self.pair_batch]]

@@ -20,13 +20,19 @@
 // everything is fp64 VALU work (MI355X: 78.6 TFLOP/s vector fp64) — 4096 hypotheses x 3 roots x 2048 matches are
 // ~0.8 GFLOP per pair, i.e. ~1 % of the time LightGlue spends on the same pair.  Phase B (one workgroup per pair) picks
 // the best split, refines and writes the mask.  No host round trip, no per-pair launch.
+// Match tables wider than GV_MAX_PTS slots take the streaming path: the correspondences are packed once into the scratch
+// buffer, phase A streams them through LDS in chunks and phase B reads them in place — the same device functions, templated
+// on where the points live, so a pair's result does not depend on the path.
 #include <math.h>
+#include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/dim_hip.h"
 #include "dim_common.h"
 
 namespace {
-constexpr int GV_MAX_PTS = 4096;   // correspondences per pair held in LDS (64 KB)
+constexpr int GV_MAX_PTS = 4096;   // correspondences per pair held in LDS (64 KB); wider tables take the streaming path
+constexpr int GV_MAX_NK = 1 << 20;   // the index width dim_op_tile_match_keys assumes
 constexpr int GV_T = 256;
 
 struct GvArgs {
@@ -36,6 +42,7 @@ struct GvArgs {
   double thr2; int iters; int splits; unsigned seed; int err_type;   // err_type 0 = Sampson, 1 = symmetric epipolar (max of the two point-line distances)
   int* best_cnt; int* best_id; double* best_F;   // phase A results [P][splits], [P][splits], [P][splits][9]
   unsigned char* mask; int* n_inl; double* F_out;  // outputs [P][nk], [P], [P][9]
+  float4* packed;                                // streaming path: (x0, y0, x1, y1) of every live match, [P][nk]
 };
 
 __device__ __forceinline__ unsigned gv_hash(unsigned seed, unsigned pair, unsigned hyp, unsigned k) {
@@ -166,17 +173,24 @@ __device__ void gv_jacobi(double* A, double* V) {
   }
 }
 
-// block-wide staging shared by both phases: gather the pair's correspondences into LDS, Hartley statistics in fp64
-struct GvShared {
-  float4 pts[GV_MAX_PTS];
+// Where a pair's correspondences live.  Up to GV_MAX_PTS of them are gathered into LDS by every workgroup (GvLdsPts: the
+// kernels for nk <= 4096).  Larger tables are gathered ONCE by gv_pack_kernel into a packed float4 [n_pairs][nk] region of
+// the scratch buffer (GvPackedPts): phase B reads it in place, phase A streams it through LDS in chunks.  Every device
+// function below is written once against `pts.at(i)`, in the same per-thread order, so a pair's result does not depend on
+// which path ran it.
+struct GvBlock {   // per-workgroup reduction space and the Hartley frames
   double red[4][48];
   double F[9];
   int ibest[4], icnt[4];
   Norm n0, n1;
   int n;
 };
+struct GvShared : GvBlock { float4 pts[GV_MAX_PTS]; };
 
-__device__ double gv_block_sum(GvShared& sh, double v, int slot) {  // all threads call; result valid after the barrier pair
+struct GvLdsPts { const GvShared& sh; __device__ __forceinline__ float4 at(int i) const { return sh.pts[i]; } };
+struct GvPackedPts { const float4* p; __device__ __forceinline__ float4 at(int i) const { return p[i]; } };
+
+__device__ double gv_block_sum(GvBlock& sh, double v, int slot) {  // all threads call; result valid after the barrier pair
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   if ((threadIdx.x & 63) == 0) sh.red[threadIdx.x >> 6][slot] = v;
   __syncthreads();
@@ -185,18 +199,13 @@ __device__ double gv_block_sum(GvShared& sh, double v, int slot) {  // all threa
   return r;
 }
 
-__device__ void gv_stage(const GvArgs& a, int pair, GvShared& sh) {
+// Hartley statistics in fp64 (thread t owns points t, t + 256, ...: it reads only what it wrote when the points are in LDS)
+template <class Pts>
+__device__ void gv_hartley(GvBlock& sh, const Pts& pts, int n) {
   const int t = threadIdx.x;
-  const int n = min(min(a.n_matches[pair], a.nk), GV_MAX_PTS);
-  const int i0 = a.pair_idx ? a.pair_idx[2 * pair] : 2 * pair, i1 = a.pair_idx ? a.pair_idx[2 * pair + 1] : 2 * pair + 1;
-  const float* k0 = a.kpts + (size_t)i0 * a.cap * 2;
-  const float* k1 = a.kpts + (size_t)i1 * a.cap * 2;
-  const long long* m = a.matches + (size_t)pair * a.nk * 2;
   double sx0 = 0, sy0 = 0, sx1 = 0, sy1 = 0;
   for (int i = t; i < n; i += GV_T) {
-    const long long ia = m[2 * i], ib = m[2 * i + 1];
-    const float4 p = make_float4(k0[2 * ia], k0[2 * ia + 1], k1[2 * ib], k1[2 * ib + 1]);
-    sh.pts[i] = p;
+    const float4 p = pts.at(i);
     sx0 += p.x; sy0 += p.y; sx1 += p.z; sy1 += p.w;
   }
   if (t == 0) sh.n = n;
@@ -205,7 +214,7 @@ __device__ void gv_stage(const GvArgs& a, int pair, GvShared& sh) {
   const double cx1 = gv_block_sum(sh, sx1, 2) * inv, cy1 = gv_block_sum(sh, sy1, 3) * inv;
   double d0 = 0, d1 = 0;
   for (int i = t; i < n; i += GV_T) {
-    const float4 p = sh.pts[i];
+    const float4 p = pts.at(i);
     d0 += sqrt((p.x - cx0) * (p.x - cx0) + (p.y - cy0) * (p.y - cy0));
     d1 += sqrt((p.z - cx1) * (p.z - cx1) + (p.w - cy1) * (p.w - cy1));
   }
@@ -217,6 +226,51 @@ __device__ void gv_stage(const GvArgs& a, int pair, GvShared& sh) {
   __syncthreads();
 }
 
+struct GvPairRows { const float* k0; const float* k1; const long long* m; };
+__device__ __forceinline__ GvPairRows gv_pair_rows(const GvArgs& a, int pair) {
+  const int i0 = a.pair_idx ? a.pair_idx[2 * pair] : 2 * pair, i1 = a.pair_idx ? a.pair_idx[2 * pair + 1] : 2 * pair + 1;
+  return GvPairRows{a.kpts + (size_t)i0 * a.cap * 2, a.kpts + (size_t)i1 * a.cap * 2, a.matches + (size_t)pair * a.nk * 2};
+}
+__device__ __forceinline__ float4 gv_gather(const GvPairRows& r, int i) {
+  const long long ia = r.m[2 * i], ib = r.m[2 * i + 1];
+  return make_float4(r.k0[2 * ia], r.k0[2 * ia + 1], r.k1[2 * ib], r.k1[2 * ib + 1]);
+}
+
+// block-wide staging of the LDS-resident path, both phases: gather the pair's correspondences into LDS, then the statistics
+__device__ void gv_stage(const GvArgs& a, int pair, GvShared& sh) {
+  const int n = min(min(a.n_matches[pair], a.nk), GV_MAX_PTS);
+  const GvPairRows rows = gv_pair_rows(a, pair);
+  for (int i = threadIdx.x; i < n; i += GV_T) sh.pts[i] = gv_gather(rows, i);
+  gv_hartley(sh, GvLdsPts{sh}, n);
+}
+
+// the 7 distinct sample indices of hypothesis `hyp` (8 attempts per draw, then the hypothesis is skipped)
+__device__ bool gv_sample(const GvArgs& a, int pair, int hyp, int n, int* idx) {
+  for (int j = 0; j < 7; ++j) {
+    int att = 0;
+    for (;;) {
+      const int cand = (int)(((unsigned long long)gv_hash(a.seed, (unsigned)pair, (unsigned)hyp, (unsigned)(j + 7 * att)) * (unsigned long long)n) >> 32);
+      bool dup = false;
+      for (int q = 0; q < j; ++q) dup = dup || idx[q] == cand;
+      if (!dup) { idx[j] = cand; break; }
+      if (++att >= 8) return false;
+    }
+  }
+  return true;
+}
+
+// candidates (normalised frame) of one minimal sample; returns the count
+template <class Pts>
+__device__ int gv_solve(const Pts& pts, const int* idx, const Norm& n0, const Norm& n1, double (*Fc)[9]) {
+  double p[7][4];
+  for (int j = 0; j < 7; ++j) {
+    const float4 q = pts.at(idx[j]);
+    p[j][0] = n0.s * (q.x - n0.cx); p[j][1] = n0.s * (q.y - n0.cy);
+    p[j][2] = n1.s * (q.z - n1.cx); p[j][3] = n1.s * (q.w - n1.cy);
+  }
+  return gv_seven_point(p, Fc);
+}
+
 __device__ int gv_count(const GvShared& sh, const double* F, double thr2, int err_type) {
   int c = 0;
   for (int i = 0; i < sh.n; ++i) {
@@ -226,49 +280,9 @@ __device__ int gv_count(const GvShared& sh, const double* F, double thr2, int er
   return c;
 }
 
-// ---- phase A: hypotheses --------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(GV_T) void gv_hypotheses_kernel(GvArgs a) {
-  __shared__ GvShared sh;
-  const int split = blockIdx.x, pair = blockIdx.y, t = threadIdx.x;
-  gv_stage(a, pair, sh);
-  const int n = sh.n;
-  int my_cnt = -1, my_id = 0x7fffffff;
-  double my_F[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  if (n >= 8) {
-    const int per = (a.iters + a.splits - 1) / a.splits;
-    const int h0 = split * per, h1 = min(a.iters, h0 + per);
-    for (int hyp = h0 + t; hyp < h1; hyp += GV_T) {
-      int idx[7];
-      bool ok = true;
-      for (int j = 0; j < 7 && ok; ++j) {
-        int att = 0;
-        for (;;) {
-          const int cand = (int)(((unsigned long long)gv_hash(a.seed, (unsigned)pair, (unsigned)hyp, (unsigned)(j + 7 * att)) * (unsigned long long)n) >> 32);
-          bool dup = false;
-          for (int q = 0; q < j; ++q) dup = dup || idx[q] == cand;
-          if (!dup) { idx[j] = cand; break; }
-          if (++att >= 8) { ok = false; break; }
-        }
-      }
-      if (!ok) continue;
-      double p[7][4];
-      for (int j = 0; j < 7; ++j) {
-        const float4 q = sh.pts[idx[j]];
-        p[j][0] = sh.n0.s * (q.x - sh.n0.cx); p[j][1] = sh.n0.s * (q.y - sh.n0.cy);
-        p[j][2] = sh.n1.s * (q.z - sh.n1.cx); p[j][3] = sh.n1.s * (q.w - sh.n1.cy);
-      }
-      double Fc[3][9];
-      const int nr = gv_seven_point(p, Fc);
-      for (int r = 0; r < nr; ++r) {
-        double F[9];
-        gv_denormalise(Fc[r], sh.n0, sh.n1, F);
-        const int c = gv_count(sh, F, a.thr2, a.err_type);
-        const int id = hyp * 3 + r;
-        if (c > my_cnt || (c == my_cnt && id < my_id)) { my_cnt = c; my_id = id; for (int j = 0; j < 9; ++j) my_F[j] = F[j]; }
-      }
-    }
-  }
-  // workgroup arg-max (count desc, id asc): wave shuffles, then the four wave winners through LDS
+// workgroup arg-max (count desc, id asc): wave shuffles, then the four wave winners through LDS; the owner writes the split's result
+__device__ void gv_split_best(const GvArgs& a, GvBlock& sh, int pair, int split, int my_cnt, int my_id, const double* my_F) {
+  const int t = threadIdx.x;
   int bc = my_cnt, bi = my_id;
   for (int o = 32; o > 0; o >>= 1) {
     const int oc = __shfl_xor(bc, o), oi = __shfl_xor(bi, o);
@@ -285,13 +299,131 @@ __global__ __launch_bounds__(GV_T) void gv_hypotheses_kernel(GvArgs a) {
   if (t == 0 && bc < 0) { const size_t o = (size_t)pair * a.splits + split; a.best_cnt[o] = -1; a.best_id[o] = 0x7fffffff; }
 }
 
-// ---- phase B: pick, refine, write the mask ----------------------------------------------------------------------------
-__global__ __launch_bounds__(GV_T) void gv_refine_kernel(GvArgs a) {
+// ---- phase A: hypotheses --------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(GV_T) void gv_hypotheses_kernel(GvArgs a) {
   __shared__ GvShared sh;
-  __shared__ double Fcur[9];
-  __shared__ int cur_cnt;
-  const int pair = blockIdx.x, t = threadIdx.x;
+  const int split = blockIdx.x, pair = blockIdx.y, t = threadIdx.x;
   gv_stage(a, pair, sh);
+  const int n = sh.n;
+  int my_cnt = -1, my_id = 0x7fffffff;
+  double my_F[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (n >= 8) {
+    const int per = (a.iters + a.splits - 1) / a.splits;
+    const int h0 = split * per, h1 = min(a.iters, h0 + per);
+    for (int hyp = h0 + t; hyp < h1; hyp += GV_T) {
+      int idx[7];
+      if (!gv_sample(a, pair, hyp, n, idx)) continue;
+      double Fc[3][9];
+      const int nr = gv_solve(GvLdsPts{sh}, idx, sh.n0, sh.n1, Fc);
+      for (int r = 0; r < nr; ++r) {
+        double F[9];
+        gv_denormalise(Fc[r], sh.n0, sh.n1, F);
+        const int c = gv_count(sh, F, a.thr2, a.err_type);
+        const int id = hyp * 3 + r;
+        if (c > my_cnt || (c == my_cnt && id < my_id)) { my_cnt = c; my_id = id; for (int j = 0; j < 9; ++j) my_F[j] = F[j]; }
+      }
+    }
+  }
+  gv_split_best(a, sh, pair, split, my_cnt, my_id, my_F);
+}
+
+// ---- streaming path (nk > GV_MAX_PTS) -----------------------------------------------------------------------------------
+// one pass: the live matches of every pair as (x0, y0, x1, y1), one 16-byte store each
+__global__ __launch_bounds__(GV_T) void gv_pack_kernel(GvArgs a) {
+  const int pair = blockIdx.y, i = blockIdx.x * GV_T + threadIdx.x;
+  const int n = min(a.n_matches[pair], a.nk);
+  if (i >= n) return;
+  a.packed[(size_t)pair * a.nk + i] = gv_gather(gv_pair_rows(a, pair), i);
+}
+
+// (four 16-byte loads in flight per thread: unrolled further, the loads cost the registers that keep two workgroups on a CU)
+__device__ __forceinline__ void gv_stream_stage(float4* dst, const GvPackedPts& pts, int first, int m) {
+#pragma unroll 4
+  for (int i = threadIdx.x; i < m; i += GV_T) dst[i] = pts.at(first + i);
+}
+
+// counts of up to three candidates over one LDS chunk (wave-wide broadcast reads, like gv_count); the roots are unrolled so
+// that the candidate matrices stay in registers
+__device__ __forceinline__ void gv_stream_score(const float4* buf, int m, const double (*F)[9], int nr, double thr2, int err_type, int* cnt) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    if (r >= nr) continue;
+    int c = 0;
+    for (int i = 0; i < m; ++i) {
+      const float4 p = buf[i];
+      c += gv_error(F[r], p.x, p.y, p.z, p.w, err_type) <= thr2 ? 1 : 0;
+    }
+    cnt[r] += c;
+  }
+}
+
+// Phase A over the packed points.  A round is 256 hypotheses (one per thread): each thread builds its candidates from seven
+// reads of the packed buffer, then the pair's points pass through LDS in chunks of C and every thread adds up integer counts.
+// NBUF 1: one buffer of C = 4096 points, two barriers per chunk.  NBUF 2: two buffers of C = 2048, the next chunk is staged
+// while this one is scored, one barrier per chunk.  Every barrier is reached by every thread: the round and chunk loops have
+// block-uniform trip counts and a thread without a hypothesis (past h1, rejected sample, no root) scores nothing (nr = 0).
+template <int C, int NBUF>
+__global__ __launch_bounds__(GV_T) void gv_hypotheses_stream_kernel(GvArgs a) {
+  static_assert((C & (C - 1)) == 0 && C * NBUF <= GV_MAX_PTS && (NBUF == 1 || NBUF == 2), "chunk staging is at most 64 KB");
+  __shared__ GvBlock sh;
+  __shared__ float4 buf[NBUF][C];
+  const int split = blockIdx.x, pair = blockIdx.y, t = threadIdx.x;
+  const int n = min(a.n_matches[pair], a.nk);   // block-uniform
+  const GvPackedPts pts{a.packed + (size_t)pair * a.nk};
+  gv_hartley(sh, pts, n);
+  int my_cnt = -1, my_id = 0x7fffffff;
+  double my_F[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (n >= 8) {
+    const Norm n0 = sh.n0, n1 = sh.n1;
+    const int per = (a.iters + a.splits - 1) / a.splits;
+    const int h0 = split * per, h1 = min(a.iters, h0 + per);
+    const int n_chunks = (n + C - 1) / C;
+    for (int base = h0; base < h1; base += GV_T) {
+      const int hyp = base + t;
+      double F[3][9];
+      int nr = 0;
+      if (hyp < h1) {
+        int idx[7];
+        if (gv_sample(a, pair, hyp, n, idx)) {
+          double Fc[3][9];
+          nr = gv_solve(pts, idx, n0, n1, Fc);
+#pragma unroll
+          for (int r = 0; r < 3; ++r) if (r < nr) gv_denormalise(Fc[r], n0, n1, F[r]);
+        }
+      }
+      int cnt[3] = {0, 0, 0};
+      if (NBUF == 1) {
+        for (int c = 0; c < n_chunks; ++c) {
+          const int m = min(C, n - c * C);
+          __syncthreads();                       // the previous chunk (or round) has been scored by everyone
+          gv_stream_stage(buf[0], pts, c * C, m);
+          __syncthreads();
+          gv_stream_score(buf[0], m, F, nr, a.thr2, a.err_type, cnt);
+        }
+      } else {
+        __syncthreads();                         // the previous round's last chunk has been scored by everyone
+        gv_stream_stage(buf[0], pts, 0, min(C, n));
+        for (int c = 0; c < n_chunks; ++c) {
+          __syncthreads();                       // chunk c is staged, chunk c - 1 has been scored: its buffer is free
+          if (c + 1 < n_chunks) gv_stream_stage(buf[(c + 1) & (NBUF - 1)], pts, (c + 1) * C, min(C, n - (c + 1) * C));
+          gv_stream_score(buf[c & (NBUF - 1)], min(C, n - c * C), F, nr, a.thr2, a.err_type, cnt);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        if (r >= nr) continue;
+        const int id = hyp * 3 + r;
+        if (cnt[r] > my_cnt || (cnt[r] == my_cnt && id < my_id)) { my_cnt = cnt[r]; my_id = id; for (int j = 0; j < 9; ++j) my_F[j] = F[r][j]; }
+      }
+    }
+  }
+  gv_split_best(a, sh, pair, split, my_cnt, my_id, my_F);
+}
+
+// ---- phase B: pick, refine, write the mask ----------------------------------------------------------------------------
+template <class Pts>
+__device__ void gv_refine(const GvArgs& a, int pair, GvBlock& sh, const Pts& pts, double* Fcur, int& cur_cnt) {
+  const int t = threadIdx.x;
   const int n = sh.n;
   unsigned char* mask = a.mask + (size_t)pair * a.nk;
   if (n < 8) {  // geometric_verification.py:107-110: not enough matches -> F = None, every match is an inlier
@@ -320,7 +452,7 @@ __global__ __launch_bounds__(GV_T) void gv_refine_kernel(GvArgs a) {
     double acc[45];
     for (int j = 0; j < 45; ++j) acc[j] = 0.0;
     for (int i = t; i < n; i += GV_T) {
-      const float4 q = sh.pts[i];
+      const float4 q = pts.at(i);
       if (!(gv_error(Fcur, q.x, q.y, q.z, q.w, a.err_type) <= a.thr2)) continue;
       const double x0 = sh.n0.s * (q.x - sh.n0.cx), y0 = sh.n0.s * (q.y - sh.n0.cy), x1 = sh.n1.s * (q.z - sh.n1.cx), y1 = sh.n1.s * (q.w - sh.n1.cy);
       const double r[9] = {x1 * x0, x1 * y0, x1, y1 * x0, y1 * y0, y1, x0, y0, 1.0};
@@ -357,14 +489,14 @@ __global__ __launch_bounds__(GV_T) void gv_refine_kernel(GvArgs a) {
     }
     __syncthreads();
     int c = 0;
-    for (int i = t; i < n; i += GV_T) { const float4 q = sh.pts[i]; c += gv_error(sh.F, q.x, q.y, q.z, q.w, a.err_type) <= a.thr2 ? 1 : 0; }
+    for (int i = t; i < n; i += GV_T) { const float4 q = pts.at(i); c += gv_error(sh.F, q.x, q.y, q.z, q.w, a.err_type) <= a.thr2 ? 1 : 0; }
     const int tot = (int)(gv_block_sum(sh, (double)c, 46) + 0.5);
     if (t == 0 && tot >= cur_cnt) { cur_cnt = tot; for (int j = 0; j < 9; ++j) Fcur[j] = sh.F[j]; }
     __syncthreads();
   }
   for (int i = t; i < a.nk; i += GV_T) {
     unsigned char v = 0;
-    if (i < n) { const float4 q = sh.pts[i]; v = gv_error(Fcur, q.x, q.y, q.z, q.w, a.err_type) <= a.thr2 ? 1 : 0; }
+    if (i < n) { const float4 q = pts.at(i); v = gv_error(Fcur, q.x, q.y, q.z, q.w, a.err_type) <= a.thr2 ? 1 : 0; }
     mask[i] = v;
   }
   if (t == 0) {
@@ -377,6 +509,24 @@ __global__ __launch_bounds__(GV_T) void gv_refine_kernel(GvArgs a) {
     for (int j = 0; j < 9; ++j) a.F_out[(size_t)pair * 9 + j] = Fcur[j] * sc;
   }
 }
+
+__global__ __launch_bounds__(GV_T) void gv_refine_kernel(GvArgs a) {
+  __shared__ GvShared sh;
+  __shared__ double Fcur[9];
+  __shared__ int cur_cnt;
+  gv_stage(a, blockIdx.x, sh);
+  gv_refine(a, blockIdx.x, sh, GvLdsPts{sh}, Fcur, cur_cnt);
+}
+
+__global__ __launch_bounds__(GV_T) void gv_refine_stream_kernel(GvArgs a) {
+  __shared__ GvBlock sh;
+  __shared__ double Fcur[9];
+  __shared__ int cur_cnt;
+  const int pair = blockIdx.x;
+  const GvPackedPts pts{a.packed + (size_t)pair * a.nk};
+  gv_hartley(sh, pts, min(a.n_matches[pair], a.nk));
+  gv_refine(a, pair, sh, pts, Fcur, cur_cnt);
+}
 }  // namespace
 
 extern "C" {
@@ -387,12 +537,26 @@ static size_t gv_scratch(int n_pairs, int splits) {
 }
 size_t dim_gv_scratch_bytes(int n_pairs) { return gv_scratch(n_pairs, 16); }
 
+// split results, then (tables wider than the LDS-resident limit) the packed points float4 [n_pairs][nk] on a 16-byte boundary
+size_t dim_gv_scratch_bytes_nk(int n_pairs, int nk) {
+  if (nk <= GV_MAX_PTS) return gv_scratch(n_pairs, 16);
+  return gv_scratch(n_pairs, 16) + 16 + (size_t)(n_pairs > 0 ? n_pairs : 0) * (size_t)nk * sizeof(float4);
+}
+
+// chunk layout of the streaming phase A: two buffers of 2048 points (the default: faster in every case of scripts/bench_gv.py, DESIGN.md
+// section 6) or one buffer of 4096; DIM_GV_STREAM_LAYOUT=single | double selects one for that A/B.  The results are the same integers.
+static bool gv_stream_double() {
+  const char* e = getenv("DIM_GV_STREAM_LAYOUT");
+  if (e && e[0] == 's') return false;
+  return true;
+}
+
 int dim_gv_fundamental(const float* kpts_tab_dev, int cap, const int32_t* pair_idx_dev, const int64_t* matches_dev,
                        const int32_t* n_matches_dev, int nk, int n_pairs, double threshold_px, int iters, int error_type, unsigned seed,
                        void* scratch_dev, size_t scratch_bytes, unsigned char* inlier_mask_dev, int32_t* n_inliers_dev, double* F_dev,
                        void* stream) {
   DIM_REQUIRE(kpts_tab_dev && matches_dev && n_matches_dev && inlier_mask_dev && n_inliers_dev && F_dev && scratch_dev, "dim_gv_fundamental: null argument");
-  DIM_REQUIRE(cap > 0 && nk > 0 && nk <= GV_MAX_PTS, "dim_gv_fundamental: nk=%d outside [1,%d]", nk, GV_MAX_PTS);
+  DIM_REQUIRE(cap > 0 && nk > 0 && nk <= GV_MAX_NK, "dim_gv_fundamental: nk=%d outside [1,%d]", nk, GV_MAX_NK);
   DIM_REQUIRE(threshold_px > 0.0 && iters >= 1 && (error_type == 0 || error_type == 1), "dim_gv_fundamental: bad threshold / iters / error_type");
   if (n_pairs <= 0) return 0;
   GvArgs a;
@@ -403,12 +567,30 @@ int dim_gv_fundamental(const float* kpts_tab_dev, int cap, const int32_t* pair_i
   splits = splits < 1 ? 1 : (splits > 16 ? 16 : splits);
   while (splits > 1 && (iters + splits - 1) / splits < GV_T) --splits;
   a.splits = splits;
-  DIM_REQUIRE(scratch_bytes >= gv_scratch(n_pairs, splits), "dim_gv_fundamental: scratch too small (%zu < %zu)", scratch_bytes, gv_scratch(n_pairs, splits));
+  const bool stream_pts = nk > GV_MAX_PTS;
+  if (!stream_pts)
+    DIM_REQUIRE(scratch_bytes >= gv_scratch(n_pairs, splits), "dim_gv_fundamental: scratch too small (%zu < %zu)", scratch_bytes, gv_scratch(n_pairs, splits));
+  else
+    DIM_REQUIRE(scratch_bytes >= dim_gv_scratch_bytes_nk(n_pairs, nk), "dim_gv_fundamental: scratch too small (%zu < dim_gv_scratch_bytes_nk(%d, %d) = %zu)",
+                scratch_bytes, n_pairs, nk, dim_gv_scratch_bytes_nk(n_pairs, nk));
   const size_t e = (size_t)n_pairs * splits;
   a.best_F = (double*)scratch_dev; a.best_cnt = (int*)(a.best_F + e * 9); a.best_id = a.best_cnt + e;
+  a.packed = nullptr;
   a.mask = inlier_mask_dev; a.n_inl = n_inliers_dev; a.F_out = F_dev;
-  hipLaunchKernelGGL(gv_hypotheses_kernel, dim3(splits, n_pairs), dim3(GV_T), 0, (hipStream_t)stream, a);
-  hipLaunchKernelGGL(gv_refine_kernel, dim3(n_pairs), dim3(GV_T), 0, (hipStream_t)stream, a);
+  hipStream_t s = (hipStream_t)stream;
+  if (!stream_pts) {
+    hipLaunchKernelGGL(gv_hypotheses_kernel, dim3(splits, n_pairs), dim3(GV_T), 0, s, a);
+    hipLaunchKernelGGL(gv_refine_kernel, dim3(n_pairs), dim3(GV_T), 0, s, a);
+  } else {
+    const uintptr_t p = (uintptr_t)scratch_dev + gv_scratch(n_pairs, 16);
+    a.packed = (float4*)((p + 15) & ~(uintptr_t)15);
+    hipLaunchKernelGGL(gv_pack_kernel, dim3((nk + GV_T - 1) / GV_T, n_pairs), dim3(GV_T), 0, s, a);
+    if (gv_stream_double())
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(gv_hypotheses_stream_kernel<2048, 2>), dim3(splits, n_pairs), dim3(GV_T), 0, s, a);
+    else
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(gv_hypotheses_stream_kernel<4096, 1>), dim3(splits, n_pairs), dim3(GV_T), 0, s, a);
+    hipLaunchKernelGGL(gv_refine_stream_kernel, dim3(n_pairs), dim3(GV_T), 0, s, a);
+  }
   DIM_LAUNCH_CHECK();
   return 0;
 }

@@ -13,8 +13,11 @@ the superpoint+lightglue pipeline, every quality level) with two differences tha
   (depth 0.9 / width 0.95 / filter 0.3), per-tile-pair vote count — stays on the device
   (``dim_op_resize_area_f32``, ``dim_sp_extract``, ``dim_lg_match``, ``dim_op_tile_pair_votes``).
 
-Per-tile geometric verification (``geometric_verification_per_tile``, MB:427-441) is cv2 RANSAC in the
-reference and is not rebuilt: with that option set the mixin defers to the base class.
+Per-tile geometric verification (``geometric_verification_per_tile``, MB:427-441) is one cv2 call per tile pair in
+the reference.  Tile pairs are pairs of one batched call here and their keypoints are in full-image coordinates, so
+a chunk's match tables go straight through ``verify.DeviceVerifier`` (``dim_gv_fundamental``, the deterministic
+estimator oracle/geom_ref.py restates; threshold ``gv_threshold_in_tiles_matching``, passed raw as MB:433 does) and
+``dim_op_filter_matches`` (MB:437-440: fewer than 15 inliers drop the whole tile pair) before the index mapping.
 """
 from __future__ import annotations
 
@@ -403,9 +406,24 @@ def ctypes_float(x):
     return ctypes.c_float(float(np.float32(x)))
 
 
+def verify_tile_chunk(lib, verifier, kt: torch.Tensor, o: dict, pidx: torch.Tensor, min_inliers_per_tile: int = 15):
+    """MB:427-440 for one chunk of tile pairs on the device: the estimator's inlier masks (``verifier.verify_batch`` on the chunk's match
+    tables; a tile pair with fewer than 8 matches gets an all-ones mask), then dim_op_filter_matches with min_inliers_per_tile and no ratio
+    rule.  Returns (verified [P, NK, 2] int64, n_verified [P] int32); a dropped tile pair has the count 0."""
+    P, NK = int(pidx.shape[0]), int(o["matches"].shape[1])
+    matches, n_matches = o["matches"][:P], o["n_matches"][:P]
+    mask = verifier.verify_batch(kt, matches, n_matches, pair_idx=pidx)["mask"]
+    ver = torch.empty_like(matches)
+    n_ver = torch.empty_like(n_matches)
+    capi.check(lib, lib.dim_op_filter_matches(capi.ptr(matches), capi.ptr(n_matches), capi.ptr(mask), NK, P, int(min_inliers_per_tile), ctypes.c_double(0.0),
+                                              capi.ptr(ver), capi.ptr(n_ver), capi.stream_ptr(matches.device)))
+    return ver, n_ver.clamp_(min=0)      # (-1 = dropped: nothing of that tile pair survives)
+
+
 def match_tile_pairs_batched(net_for, features0: dict, features1: dict, tile_pairs: Sequence[Tuple[int, int]], device,
-                             pair_batch: int = 8, select_unique: bool = True) -> np.ndarray:
-    """The loop of MB:414-460, batched.  ``net_for(n_kpts, n_pairs)`` returns a LightGlueHIP sized for it."""
+                             pair_batch: int = 8, select_unique: bool = True, verifier=None, min_inliers_per_tile: int = 15) -> np.ndarray:
+    """The loop of MB:414-460, batched.  ``net_for(n_kpts, n_pairs)`` returns a LightGlueHIP sized for it.  ``verifier`` (a verify.DeviceVerifier
+    or verify.AllInliersVerifier): per-tile geometric verification, MB:427-440 (verify_tile_chunk)."""
     full = np.array([], dtype=np.int64).reshape(0, 2)
     if len(tile_pairs) == 0:
         return full
@@ -442,8 +460,11 @@ def match_tile_pairs_batched(net_for, features0: dict, features1: dict, tile_pai
         chunk = tile_pairs[s:s + pair_batch]
         pidx = torch.tensor([[row0[a], row1[b]] for a, b in chunk], dtype=torch.int32, device=dev).contiguous()
         o = net.match_batch_guarded(kt_d, dt_d, nt_d, st_d, pair_idx=pidx, n_pairs=len(chunk), logger=logger)
-        cnt = o["n_matches"].cpu().numpy()
-        m = o["matches"].cpu().numpy()
+        rows, n_rows = o["matches"], o["n_matches"]
+        if verifier is not None:
+            rows, n_rows = verify_tile_chunk(verifier.lib, verifier, kt_d, o, pidx, min_inliers_per_tile)
+        cnt = n_rows.cpu().numpy()
+        m = rows.cpu().numpy()
         for j, (a, b) in enumerate(chunk):
             c = m[j, : int(cnt[j])]
             orig = np.zeros_like(c)
@@ -502,13 +523,14 @@ def device_unique_match_rows(lib, keys: torch.Tensor, n_slots: int, cap_m: int, 
 
 
 def match_tile_pairs_batched_device(net_for, f0: dict, f1: dict, tile_pairs: Sequence[Tuple[int, int]], pair_batch: int = 8,
-                                    select_unique: bool = True) -> torch.Tensor:
+                                    select_unique: bool = True, verifier=None, min_inliers_per_tile: int = 15) -> torch.Tensor:
     """match_tile_pairs_batched with the feature tables ALREADY in HBM and the result left there (round 4: pipeline.TiledPairPipeline holds every
     image's merged tile table in its exchange buffer; the numpy version re-uploads 33 MB per image and image pair and unpacks on the host —
     two thirds of config 5's 108 ms per image pair).  f0 / f1: {"keypoints" [N, 2] f32, "descriptors_nd" [N, D] f32, "tile_idx" [N] f32
     (device tensors), "image_size" (2,)}.  Returns (M, 2) int64 on the device, identical to the numpy version's array (same tile
     tables, same LightGlue calls; rows unique and in np.unique(axis=0)'s lexicographic order).  Round 6: the grouping by tile, the index
-    mapping and the unique are the library's own kernels (csrc/sort_ops.hip) — no torch.argsort / torch.unique on the path."""
+    mapping and the unique are the library's own kernels (csrc/sort_ops.hip) — no torch.argsort / torch.unique on the path.
+    ``verifier``: per-tile geometric verification on the device (verify_tile_chunk) between the matcher and the index mapping."""
     from . import capi
     dev = f0["keypoints"].device
     empty = torch.empty(0, 2, dtype=torch.int64, device=dev)
@@ -552,7 +574,10 @@ def match_tile_pairs_batched_device(net_for, f0: dict, f1: dict, tile_pairs: Seq
         chunk = tile_pairs[s:s + pair_batch]
         pidx = torch.tensor([[row0[a], row1[b]] for a, b in chunk], dtype=torch.int32, device=dev).contiguous()
         o = net.match_batch_guarded(kt, dt, nt, st, pair_idx=pidx, n_pairs=len(chunk), logger=logger)
-        capi.check(lib, lib.dim_op_tile_match_keys(capi.ptr(o["matches"]), capi.ptr(o["n_matches"]), capi.ptr(it), capi.ptr(pidx), capi.ptr(zero_slot), len(chunk), NK, cap,
+        rows_c, n_rows = o["matches"], o["n_matches"]
+        if verifier is not None:
+            rows_c, n_rows = verify_tile_chunk(lib, verifier, kt, o, pidx, min_inliers_per_tile)
+        capi.check(lib, lib.dim_op_tile_match_keys(capi.ptr(rows_c), capi.ptr(n_rows), capi.ptr(it), capi.ptr(pidx), capi.ptr(zero_slot), len(chunk), NK, cap,
                                                    capi.ptr(keys[s:s + len(chunk)]), capi.stream_ptr(dev)))
     cap_m = len(tile_pairs) * NK
     rows = torch.empty(1, cap_m, 2, dtype=torch.int64, device=dev)
@@ -597,6 +622,22 @@ class BatchedTileMatchingMixin:
                 device=self._device if isinstance(self._device, (str, torch.device)) else "cuda", lib=self._lib)
         return self._tile_preselector
 
+    def _tile_verifier(self):
+        """The estimator of ``geometric_verification_per_tile`` (MB:427-435), one per matcher: the device RANSAC at the raw
+        ``gv_threshold_in_tiles_matching`` (no quality scale, as MB:433 passes it), otherwise as BatchedImageMatcher builds its verifier
+        (Sampson error, 2048 hypotheses, seed 0); geom_verification NONE keeps every match (geometric_verification.py's NONE branch)."""
+        if getattr(self, "_tile_gv", None) is None:
+            from .verify import AllInliersVerifier, DeviceVerifier
+            general = self.config["general"]
+            gv = general.get("geom_verification", "MAGSAC")
+            if getattr(gv, "name", str(gv)).upper() == "NONE":
+                self._tile_gv = AllInliersVerifier(lib=self._lib)
+            else:
+                dev = self._device if isinstance(self._device, (str, torch.device)) else "cuda"
+                self._tile_gv = DeviceVerifier(threshold=float(general.get("gv_threshold_in_tiles_matching", 4)), iters=2048, error_type="sampson", seed=0,
+                                               device=dev, lib=self._lib)
+        return self._tile_gv
+
     def tile_selection(self, img0, img1, method: str, image0: Optional[np.ndarray] = None, image1: Optional[np.ndarray] = None):
         """tile_selection (MB:989-1140) -> sorted list of (tile0, tile1)."""
         general = self.config["general"]
@@ -623,12 +664,11 @@ class BatchedTileMatchingMixin:
     @torch.no_grad()
     def _match_by_tile(self, img0, img1, features0: dict, features1: dict, method="PRESELECTION", select_unique: bool = True) -> np.ndarray:
         general = self.config["general"]
-        if general.get("geometric_verification_per_tile"):
-            return super()._match_by_tile(img0, img1, features0, features1, method=method, select_unique=select_unique)
+        verifier = self._tile_verifier() if general.get("geometric_verification_per_tile") else None
         name = getattr(method, "name", method)
         tile_pairs = self.tile_selection(img0, img1, name)
         if len(tile_pairs) == 0:
             logger.debug("No tile pairs selected.")
             return np.array([], dtype=np.int64).reshape(0, 2)
         dev = self._device if isinstance(self._device, (str, torch.device)) else "cuda"
-        return match_tile_pairs_batched(self._ensure_pairs, features0, features1, tile_pairs, dev, self.tile_pair_batch, select_unique)
+        return match_tile_pairs_batched(self._ensure_pairs, features0, features1, tile_pairs, dev, self.tile_pair_batch, select_unique, verifier=verifier)

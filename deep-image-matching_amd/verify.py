@@ -41,7 +41,7 @@ class DeviceVerifier:
         if error_type not in ERROR_TYPES:
             raise ValueError(f"error_type must be one of {sorted(ERROR_TYPES)}")
         self.error_type = ERROR_TYPES[error_type]
-        self.lib.dim_gv_scratch_bytes.restype = ctypes.c_size_t
+        self.lib.dim_gv_scratch_bytes_nk.restype = ctypes.c_size_t
         self._scratch: Optional[torch.Tensor] = None
 
     def _stream(self):
@@ -52,12 +52,13 @@ class DeviceVerifier:
                      out=None):
         """kpts_tab [n_img, cap, 2] f32; matches [P, NK, 2] int64 and n_matches [P] int32 as written by dim_lg_match;
         pair_idx [P, 2] int32 or None (pair p = slots 2p, 2p+1).  Returns device tensors
-        {"mask" [P, NK] uint8, "n_inliers" [P] int32, "F" [P, 3, 3] float64}."""
+        {"mask" [P, NK] uint8, "n_inliers" [P] int32, "F" [P, 3, 3] float64}.  Any NK up to 2**20: tables wider than 4096 take the
+        library's streaming kernels, with the same results."""
         assert kpts_tab.dtype == torch.float32 and matches.dtype == torch.int64 and n_matches.dtype == torch.int32
         assert kpts_tab.is_contiguous() and matches.is_contiguous() and n_matches.is_contiguous()
         P, NK = matches.shape[0], matches.shape[1]
         dev = matches.device
-        need = int(self.lib.dim_gv_scratch_bytes(P))
+        need = int(self.lib.dim_gv_scratch_bytes_nk(int(P), int(NK)))      # split results; tables wider than 4096 add the packed points
         if self._scratch is None or self._scratch.numel() < need or self._scratch.device != dev:
             self._scratch = torch.empty(need, dtype=torch.uint8, device=dev)
         if out is None:
@@ -83,6 +84,19 @@ class DeviceVerifier:
         o = self.verify_batch(kt.to(self.device), mt.to(self.device), torch.tensor([S], dtype=torch.int32, device=self.device))
         mask = o["mask"][0, :S].cpu().numpy().astype(bool)
         return (o["F"][0].cpu().numpy() if S >= 8 else None), mask
+
+
+class AllInliersVerifier:
+    """geom_verification NONE behind the DeviceVerifier interface: every live match is an inlier (the reference's NONE branch returns an
+    all-ones mask); the accept rules that follow the estimator still apply."""
+
+    def __init__(self, lib=None):
+        self.lib = lib if lib is not None else capi.load()
+
+    def verify_batch(self, kpts_tab, matches, n_matches, pair_idx=None, out=None):
+        P, NK = matches.shape[0], matches.shape[1]
+        mask = (torch.arange(NK, device=matches.device)[None, :] < n_matches[:, None]).to(torch.uint8).contiguous()
+        return {"mask": mask, "n_inliers": n_matches.clamp(max=NK), "F": torch.zeros(P, 3, 3, dtype=torch.float64, device=matches.device)}
 
 
 class _Null:

@@ -491,16 +491,20 @@ int dim_op_retrieval_topk(const float* query_dev, int nq, const float* db_dev, i
  * confidence) that follows _match_pairs in the reference (utils/geometric_verification.py:45-179, called at
  * matchers/matcher_base.py:311): a batched fundamental-matrix RANSAC straight on dim_lg_match's device outputs.
  * Inputs: the feature table's keypoints [n_img][cap][2], pair_idx [n_pairs][2] (NULL = slots 2p, 2p+1), matches
- * [n_pairs][nk][2] int64 + n_matches [n_pairs] exactly as dim_lg_match wrote them (nk <= 4096).
+ * [n_pairs][nk][2] int64 + n_matches [n_pairs] exactly as dim_lg_match wrote them, 1 <= nk <= 1 << 20.  Tables with
+ * nk <= 4096 keep a pair's correspondences in LDS; wider ones are packed once into the scratch buffer and streamed through
+ * LDS in chunks.  The estimator and its results are the same on both paths.
  * threshold_px as the reference passes it (gv_threshold x quality scale); iters = number of 7-point hypotheses (the
  * reference's max_iters is 10000); error_type 0 = Sampson distance (USAC / pydegensac family), 1 = symmetric
  * epipolar distance (max of the two point-line distances, cv2.RANSAC); seed makes the sampling reproducible.
  * Outputs: inlier_mask [n_pairs][nk] uint8 (0 beyond n_matches), n_inliers [n_pairs], F [n_pairs][9] fp64 row-major
  * acting on pixel coordinates (x1^T F x0 = 0, scaled to F33 = 1 when possible; zeros when the pair has < 8 matches, in
  * which case every match is an inlier as in geometric_verification.py:107-110).
- * scratch: dim_gv_scratch_bytes(n_pairs) bytes of device memory.  The estimator is deterministic and restated in
+ * scratch: dim_gv_scratch_bytes_nk(n_pairs, nk) bytes of device memory (the split results, plus the packed points when
+ * nk > 4096); dim_gv_scratch_bytes(n_pairs) is that size for nk <= 4096.  The estimator is deterministic and restated in
  * numpy by oracle/geom_ref.py; it is NOT result-identical to cv2's MAGSAC (no two RANSACs are). */
 size_t dim_gv_scratch_bytes(int n_pairs);
+size_t dim_gv_scratch_bytes_nk(int n_pairs, int nk);
 int dim_gv_fundamental(const float* kpts_tab_dev, int cap, const int32_t* pair_idx_dev, const int64_t* matches_dev,
                        const int32_t* n_matches_dev, int nk, int n_pairs, double threshold_px, int iters, int error_type, unsigned seed,
                        void* scratch_dev, size_t scratch_bytes, unsigned char* inlier_mask_dev, int32_t* n_inliers_dev, double* F_dev,
