@@ -233,6 +233,63 @@ int dim_op_simple_nms_f32(const float* score_map, float* out, int batch, int H, 
   return launch_nms(score_map, out, batch, H, W, radius, (hipStream_t)stream);
 }
 
+// Keypoint selection as the extractors run it (sp_api.hip / aliked_api.hip): launch_select_ex -> launch_topk [-> launch_topk_zero_fill], on tables
+// carved out of the caller's workspace (256-byte aligned pieces; nothing is allocated here).
+namespace {
+struct SelectTopkWs {
+  size_t rowcount, rowoff, ncand, cand_score, cand_idx, keys, total;   // byte offsets
+};
+SelectTopkWs select_topk_ws(int batch, int H, int W, int k) {
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t rows = (size_t)batch * H, px = rows * W;
+  SelectTopkWs w;
+  w.rowcount = 0;
+  w.rowoff = w.rowcount + up(rows * 4);
+  w.ncand = w.rowoff + up(rows * 4);
+  w.cand_score = w.ncand + up((size_t)batch * 4);
+  w.cand_idx = w.cand_score + up(px * 4);
+  w.keys = w.cand_idx + up(px * 4);
+  w.total = w.keys + up(topk_scratch_keys(batch, k) * 8);
+  return w;
+}
+}  // namespace
+
+size_t dim_op_select_topk_workspace_bytes(int batch, int H, int W, int k) {
+  if (batch <= 0 || H <= 0 || W <= 0) return 0;
+  return select_topk_ws(batch, H, W, k).total;
+}
+
+int dim_op_select_topk_f32(const float* nms, int batch, int H, int W, float threshold, const float* threshold_dev, int border, int k,
+                           int capacity, int sort_always, int zero_fill, void* workspace, float* kpts_xy, float* scores, int32_t* n_out,
+                           int32_t* n_candidates, void* stream) {
+  DIM_REQUIRE(nms && workspace && kpts_xy && scores && n_out, "dim_op_select_topk_f32: null argument");
+  DIM_REQUIRE(batch > 0 && H > 0 && W > 0 && (long long)batch * H * W <= 0x7fffffffLL, "dim_op_select_topk_f32: bad map size %d x %d x %d", batch, H, W);
+  DIM_REQUIRE(capacity > 0 && k != 0 && border >= 0, "dim_op_select_topk_f32: capacity %d must be > 0, k %d non-zero (negative: keep all), border %d >= 0", capacity, k, border);
+  DIM_REQUIRE(k <= capacity, "dim_op_select_topk_f32: k %d > capacity %d", k, capacity);
+  DIM_REQUIRE(!(zero_fill && threshold_dev), "dim_op_select_topk_f32: zero_fill takes the scalar threshold only");
+  if (zero_fill) DIM_REQUIRE((long long)k <= (long long)H * W, "selected index k out of range: top_k %d > %d x %d pixels", k, H, W);   // launch_topk_zero_fill's check, before anything runs
+  const SelectTopkWs w = select_topk_ws(batch, H, W, k);
+  char* base = (char*)workspace;
+  int* ncand = n_candidates ? (int*)n_candidates : (int*)(base + w.ncand);
+  unsigned long long* keys = topk_scratch_keys(batch, k) ? (unsigned long long*)(base + w.keys) : nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  int rc = launch_select_ex(nms, batch, H, W, threshold, threshold_dev, border, (int*)(base + w.rowcount), (int*)(base + w.rowoff), ncand,
+                            (float*)(base + w.cand_score), (int*)(base + w.cand_idx), 0, s);
+  if (rc != 0) return rc;
+  rc = launch_topk((const float*)(base + w.cand_score), (const int*)(base + w.cand_idx), ncand, batch, H, W, k, capacity, kpts_xy, scores, (int*)n_out,
+                   keys, sort_always ? 1 : 0, s);
+  if (rc != 0) return rc;
+  if (zero_fill) rc = launch_topk_zero_fill(nms, batch, H, W, threshold, border, k, capacity, kpts_xy, scores, (int*)n_out, s);
+  return rc;
+}
+
+int dim_op_sample_descriptors_f32(const float* dense_nhwc, const float* kpts_xy, const int32_t* n_kpts, float* desc, int batch, int h, int w,
+                                  int capacity, int fix_sampling, void* stream) {
+  DIM_REQUIRE(dense_nhwc && kpts_xy && n_kpts && desc, "dim_op_sample_descriptors_f32: null argument");
+  DIM_REQUIRE(batch > 0 && h > 0 && w > 0 && capacity > 0, "dim_op_sample_descriptors_f32: bad size (batch %d, %d x %d cells, capacity %d)", batch, h, w, capacity);
+  return launch_sample_desc(dense_nhwc, kpts_xy, (const int*)n_kpts, desc, batch, h, w, capacity, fix_sampling, (hipStream_t)stream);
+}
+
 // Op-level handles: a host struct holding the pre-split device operand for the precision mode that was active
 // at creation (dim_tune_set key 1: 2 = fp16x3, 1 = bf16x6).
 static int x3_create(const float* w_kn_host, int K, int N, void** out_dev, int* n_pad_out, int kperm);

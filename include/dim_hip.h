@@ -385,6 +385,33 @@ int dim_op_conv3x3_nhwc_f32(const float* in, const float* w_tap_cin_cout, const 
  * outputs; ALIKED: sigmoids) — the kernel keeps a per-pixel mark in the sign bit. */
 int dim_op_simple_nms_f32(const float* score_map, float* out, int batch, int H, int W, int radius, void* stream);
 
+/* Keypoint selection on [batch][H][W] NMS maps, the chain dim_sp_extract and dim_aliked_extract run after the NMS (csrc/sp_post.hip: count / scan /
+ * emit rows, top-k, zero fill; several launches).  Per image:
+ *   candidates = the pixels with  v > threshold  and  border <= y < H - border,  border <= x < W - border,  in row-major order; n of them.
+ *                threshold_dev (device, one float per image) replaces `threshold` when it is not NULL.
+ *   k < 0, or n <= k without sort_always:  the first min(n, capacity) candidates, row-major (SPN:75-76, torch.nonzero order).
+ *   otherwise:                             the min(n, k) highest, score descending, equal scores by ascending pixel index (y * W + x).
+ *   zero_fill (DKD's top-k mode, ALN:150-151; scalar threshold only, k <= H * W): an image that kept fewer than k is filled up to k with the
+ *                FIRST NON-CANDIDATE PIXELS IN ROW-MAJOR ORDER, border pixels included, each with score 0.  (torch.topk takes some zero-score
+ *                pixels there too; which ones is an accident of its sort.)
+ * DOMAIN: scores and thresholds must be >= +0 (softmax / sigmoid outputs and 0 at suppressed pixels): the sort key is the score's bit pattern,
+ * which orders like the value only for non-negative floats.  k != 0, k <= capacity, k <= 32768; H * W * batch < 2^31.
+ * Outputs (device): kpts_xy [batch][capacity][2] = (x, y) as floats, scores [batch][capacity], n_out [batch]; rows at or past n_out[b] are not
+ * written.  n_candidates [batch] (NULL: not reported) receives n, also when the output was truncated to the capacity.
+ * workspace: dim_op_select_topk_workspace_bytes(batch, H, W, k) bytes of device memory, 16-byte aligned; it may be reused by later calls of any
+ * shape that fits (nothing is read from it before it is written).  nms must be 16-byte aligned.  The call only enqueues work on `stream`. */
+size_t dim_op_select_topk_workspace_bytes(int batch, int H, int W, int k);
+int dim_op_select_topk_f32(const float* nms, int batch, int H, int W, float threshold, const float* threshold_dev, int border, int k, int capacity,
+                           int sort_always, int zero_fill, void* workspace, float* kpts_xy, float* scores, int32_t* n_out, int32_t* n_candidates,
+                           void* stream);
+
+/* SuperPoint's descriptor sampling (SPN:81-98,215; fix_sampling != 0: the variant of extractors/superpoint.py:16-27) as one kernel: the dense
+ * map dense_nhwc [batch][h][w][256] (NOT normalised: every cell is L2-normalised on the fly, eps 1e-12) is sampled bilinearly (zero padding)
+ * at the first n_kpts[b] <= capacity keypoints of kpts_xy [batch][capacity][2] (pixels of the 8h x 8w image) and L2-normalised again:
+ * desc [batch][capacity][256]; rows at or past n_kpts[b] are not written.  A keypoint whose cells are all zero gives a zero descriptor. */
+int dim_op_sample_descriptors_f32(const float* dense_nhwc, const float* kpts_xy, const int32_t* n_kpts, float* desc, int batch, int h, int w,
+                                  int capacity, int fix_sampling, void* stream);
+
 /* The same convolution on the 16-bit matrix cores at fp32 accuracy (csrc/conv_x6.hip): weights are pre-split from
  * the reference's OIHW fp32 layout by dim_convx6_create for the active split mode (opaque handle, free with
  * dim_x3_destroy). */

@@ -332,3 +332,359 @@ def _ffn_fused_case(lib, M, K, seed, device="cpu"):
         lib.dim_x3_destroy(h0); lib.dim_x3_destroy(h3)
     h = torch.nn.functional.gelu(torch.nn.functional.layer_norm(A.double() @ W0.double() + b0.double(), (512,), gamma.double(), beta.double(), 1e-5))
     return C.cpu(), R.double() + h @ W3.double() + b3.double()
+
+
+# ---------------------------------------------------------------------------------------------------------------- keypoint selection
+# dim_op_select_topk_f32 = launch_select_ex -> launch_topk [-> launch_topk_zero_fill] (csrc/sp_post.hip), the chain between the NMS and the
+# descriptor head of both extractors.  The reference is exact (no arithmetic, only comparisons), so every comparison below is bit for bit.
+# Domain: scores >= 0 and thresholds >= 0 (the sort key is the score's bit pattern; include/dim_hip.h).
+I32_SENTINEL = -7
+_vp, _ci = ctypes.c_void_p, ctypes.c_int
+
+
+def _bind_selection(lib):
+    """Explicit argument types: a bare Python float would otherwise be passed as an int."""
+    lib.dim_op_select_topk_workspace_bytes.argtypes = [_ci, _ci, _ci, _ci]
+    lib.dim_op_select_topk_workspace_bytes.restype = ctypes.c_size_t
+    lib.dim_op_select_topk_f32.argtypes = [_vp, _ci, _ci, _ci, ctypes.c_float, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp]
+    lib.dim_op_select_topk_f32.restype = _ci
+    lib.dim_op_sample_descriptors_f32.argtypes = [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp]
+    lib.dim_op_sample_descriptors_f32.restype = _ci
+
+
+def score_map(H, W, seed, levels=None, density=None, value=None):
+    """One H x W map: rand * 0.9 + 0.05, optionally quantised to `levels` values (round(m * L) / L + 0.01: ties everywhere), thinned to `density`
+    by zeroing, or constant `value`."""
+    g = torch.Generator().manual_seed(seed)
+    m = torch.rand(H, W, generator=g) * 0.9 + 0.05
+    if value is not None:
+        m = torch.full((H, W), float(value))
+    if levels is not None:
+        m = (m * levels).round() / levels + 0.01
+    if density is not None:
+        m = torch.where(torch.rand(H, W, generator=g) < density, m, torch.zeros(()))
+    return m
+
+
+@functools.lru_cache(maxsize=None)
+def select_maps(name):
+    """The crafted maps of the selection cases, [batch][H][W] (cached: read only)."""
+    if name == "equal":          # all scores equal: the radix select has to walk the four index bytes
+        return score_map(72, 100, 0, value=0.5)[None]
+    if name == "ties":           # six score levels: the k-th key falls inside a tie group
+        return score_map(100, 132, 1, levels=6)[None]
+    if name == "n_near_k":
+        return score_map(96, 128, 2, density=0.35)[None]
+    if name == "handover":       # n ~ 4800 around k = 4096
+        return score_map(80, 100, 3, density=0.6)[None]
+    if name == "mixed":          # per-image branches inside one launch: empty, under k, over k, ties, a single pixel
+        one = torch.zeros(90, 124)
+        one[40, 77] = 0.625
+        return torch.stack([torch.zeros(90, 124), score_map(90, 124, 4, density=0.05), score_map(90, 124, 5, density=0.9),
+                            score_map(90, 124, 6, levels=4), one])
+    if name in ("mixed_sparse", "mixed_dense", "mixed_ties"):
+        return select_maps("mixed")[{"mixed_sparse": 1, "mixed_dense": 2, "mixed_ties": 3}[name]][None].contiguous()
+    if name == "keep_all":
+        return torch.stack([score_map(50, 70, 7, density=0.5), score_map(50, 70, 8, density=0.5)])
+    if name == "wide1300":       # W % 4 == 0: the float4 row loop's second 1024-column step
+        return score_map(6, 1300, 9)[None]
+    if name == "wide1301":       # its scalar twin
+        return score_map(6, 1301, 10)[None]
+    if name == "w260":           # just past one 256-column group
+        return torch.stack([score_map(37, 260, 11), score_map(37, 260, 12)])
+    if name == "tall":           # 1030 rows: scan_rows_kernel sums two rows per thread
+        return torch.stack([score_map(1030, 8, 13, density=0.5), score_map(1030, 8, 14, density=0.5)])
+    if name == "thr_dev":
+        return torch.stack([score_map(60, 84, 15 + i) for i in range(3)])
+    if name == "small":
+        return score_map(20, 30, 18)[None]
+    if name == "big_d07":
+        return score_map(200, 200, 19, density=0.7)[None]
+    if name == "big_full":
+        return score_map(200, 200, 20)[None]
+    if name == "big_ties":
+        return score_map(200, 200, 21, levels=3)[None]
+    if name == "occupancy128":   # 128 images: every selection kernel has at least 128 workgroups in flight
+        return torch.stack([score_map(64, 96, 100 + i, levels=50) for i in range(128)])
+    if name == "occupancy16":
+        return torch.stack([score_map(100, 132, 300 + i, levels=6) for i in range(16)])
+    raise KeyError(name)
+
+
+def select_count(name, thr, border):
+    """Number of candidates of a one-image map (for the cases whose k is derived from it)."""
+    return int(select_topk_reference(select_maps(name), [thr], border, -1, 1 << 30, 0, 0)[3][0])
+
+
+def select_topk_reference(maps, thr, border, k, capacity, sort_always, zero_fill):
+    """The rule of include/dim_hip.h, per image -> (pixel indices, scores, kept, n) lists.  thr: one float per image."""
+    B, H, W = maps.shape
+    ys, xs = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+    inside = ((ys >= border) & (ys < H - border) & (xs >= border) & (xs < W - border)).reshape(-1)
+    idxs, scs, kepts, ns = [], [], [], []
+    for b in range(B):
+        v = maps[b].reshape(-1)
+        mask = (v > torch.tensor(thr[b], dtype=torch.float32)) & inside
+        cand = mask.nonzero()[:, 0]
+        n = int(cand.numel())
+        if k < 0 or (n <= k and not sort_always):
+            keep = cand[:min(n, capacity)]
+        else:   # score descending, index ascending among equal scores: a stable sort of the row-major list
+            keep = cand[torch.sort(v[cand], descending=True, stable=True)[1]][:min(n, k)]
+        sc = v[keep]
+        kept = int(keep.numel())
+        if zero_fill and kept < k:
+            fill = (~mask).nonzero()[:k - kept, 0]
+            keep, sc = torch.cat([keep, fill]), torch.cat([sc, torch.zeros(fill.numel())])
+            kept = int(keep.numel())
+        idxs.append(keep); scs.append(sc); kepts.append(kept); ns.append(n)
+    return idxs, scs, kepts, ns
+
+
+class SelectBuffers:
+    """Workspace and the four output buffers (each followed by a guard band) of dim_op_select_topk_f32.  A fresh workspace is filled with 0xff
+    bytes: a key table that is read before it is written then holds keys above every real one."""
+
+    def __init__(self, lib, batch, H, W, k, capacity, device):
+        _bind_selection(lib)
+        self.batch, self.capacity, self.limits = batch, capacity, (batch, H, W, k)
+        self.ws = torch.full((int(lib.dim_op_select_topk_workspace_bytes(batch, H, W, k)) + 16,), 0xff, dtype=torch.uint8, device=device)
+        self.kp = torch.empty(batch * capacity * 2 + GUARD_ELEMS, device=device)
+        self.sc = torch.empty(batch * capacity + GUARD_ELEMS, device=device)
+        self.n = torch.empty(batch + GUARD_ELEMS, dtype=torch.int32, device=device)
+        self.nc = torch.empty(batch + GUARD_ELEMS, dtype=torch.int32, device=device)
+        self.refill()
+
+    def refill(self):
+        self.kp.fill_(SENTINEL); self.sc.fill_(SENTINEL); self.n.fill_(I32_SENTINEL); self.nc.fill_(I32_SENTINEL)
+
+    def cpu(self):
+        """Copies (also on the CPU: the buffers may be re-filled and used again)."""
+        return tuple(t.to("cpu", copy=True) for t in (self.kp, self.sc, self.n, self.nc))
+
+
+class SelectResult(NamedTuple):
+    raws: tuple          # per run: (kpts, scores, n_out, n_candidates) full buffers, guard bands included (CPU)
+    ref: tuple           # select_topk_reference's lists
+    shape: tuple         # (batch, H, W, capacity)
+
+    @property
+    def repeatable(self):
+        return all(all(torch.equal(a, b) for a, b in zip(self.raws[0], r)) for r in self.raws[1:])
+
+    def check(self):
+        """Everything the selection promises, exactly: counts, coordinates, score bits, untouched rows past n_out, untouched guard bands, and the
+        same bits from every run."""
+        B, H, W, cap = self.shape
+        idxs, scs, kepts, ns = self.ref
+        for kp, sc, n_out, n_cand in self.raws:
+            assert n_cand[:B].tolist() == ns, ("n_candidates", n_cand[:B].tolist(), ns)
+            assert n_out[:B].tolist() == kepts, ("n_out", n_out[:B].tolist(), kepts)
+            assert bool((n_out[B:] == I32_SENTINEL).all()) and bool((n_cand[B:] == I32_SENTINEL).all()), "guard band of the counts was written"
+            assert bool((kp[B * cap * 2:] == SENTINEL).all()) and bool((sc[B * cap:] == SENTINEL).all()), "guard band of the tables was written"
+            kp, sc = kp[:B * cap * 2].view(B, cap, 2), sc[:B * cap].view(B, cap)
+            for b in range(B):
+                m = kepts[b]
+                want = torch.stack([(idxs[b] % W).float(), (idxs[b] // W).float()], dim=1)
+                assert torch.equal(kp[b, :m], want), ("keypoints of image", b, int((kp[b, :m] != want).any(dim=1).nonzero()[0]))
+                assert torch.equal(sc[b, :m].view(torch.int32), scs[b].view(torch.int32)), ("scores of image", b)
+                assert bool((kp[b, m:] == SENTINEL).all()) and bool((sc[b, m:] == SENTINEL).all()), ("rows past n_out were written, image", b)
+        assert self.repeatable, "two runs on the same inputs differ"
+
+
+def select_topk_case(lib, maps, thr, border, k, capacity, sort_always, zero_fill, thr_dev=None, device="cpu", runs=1, bufs=None):
+    """dim_op_select_topk_f32 on `maps` [batch][H][W] vs select_topk_reference.  thr_dev: a list with one threshold per image (passed on the
+    device; replaces thr).  bufs: a SelectBuffers to REUSE (re-filled with SENTINEL, workspace left as the previous call left it); by default
+    every run gets fresh buffers and a fresh, poisoned workspace."""
+    _bind_selection(lib)
+    B, H, W = maps.shape
+    md = maps.to(device).contiguous()
+    td = torch.tensor(thr_dev, dtype=torch.float32).to(device) if thr_dev is not None else None
+    raws = []
+    for _ in range(runs):
+        if bufs is None:
+            bf = SelectBuffers(lib, B, H, W, k, capacity, device)
+        else:
+            bf = bufs
+            assert bf.batch == B and bf.capacity == capacity
+            assert int(lib.dim_op_select_topk_workspace_bytes(B, H, W, k)) <= bf.ws.numel()
+            bf.refill()
+        rc = lib.dim_op_select_topk_f32(p(md), B, H, W, float(thr), p(td), border, k, capacity, sort_always, zero_fill, p(bf.ws), p(bf.kp), p(bf.sc),
+                                        p(bf.n), p(bf.nc), None)
+        assert rc == 0, lib.dim_last_error()
+        _sync(device)
+        raws.append(bf.cpu())
+    per_image = [float(t) for t in thr_dev] if thr_dev is not None else [float(thr)] * B
+    return SelectResult(tuple(raws), select_topk_reference(maps, per_image, border, k, capacity, sort_always, zero_fill), (B, H, W, capacity))
+
+
+def _select_cases():
+    """(id, map name, thr, border, k, capacity, sort_always, zero_fill, thr_dev); k may be a function of the candidate count n."""
+    c = []
+    for k in (300, 4096, 4097, 5000):
+        c.append((f"equal-k{k}", "equal", 0.0, 0, k, k, 0, 0, None))
+    for k in (1000, 4096, 4097, 8192, 8193):
+        c.append((f"ties-k{k}", "ties", 0.0, 2, k, k, 0, 0, None))
+    n = select_count("n_near_k", 0.005, 4)
+    assert 3000 < n < 4096, n
+    for dk in (-1, 0, 1):
+        for sa, zf in ((0, 0), (1, 0), (1, 1)):
+            c.append((f"n_near_k-n{dk:+d}-s{sa}z{zf}", "n_near_k", 0.005, 4, n + dk, n + 1, sa, zf, None))
+    for k in (4095, 4096, 4097):
+        for sa, zf in ((0, 0), (1, 1)):
+            c.append((f"handover-k{k}-s{sa}z{zf}", "handover", 0.0, 0, k, 8000, sa, zf, None))
+    for k in (500, 4096, 6000):
+        for sa, zf in ((0, 0), (1, 0), (1, 1)):
+            c.append((f"mixed-k{k}-s{sa}z{zf}", "mixed", 0.0, 3, k, k, sa, zf, None))
+    for cap in (1000, 4096):
+        c.append((f"keep_all-cap{cap}", "keep_all", 0.0, 0, -1, cap, 0, 0, None))
+    c.append(("wide1300", "wide1300", 0.0, 1, 200, 200, 0, 0, None))
+    c.append(("wide1301", "wide1301", 0.0, 1, 200, 200, 0, 0, None))
+    c.append(("w260", "w260", 0.0, 5, 300, 300, 1, 1, None))
+    c.append(("tall", "tall", 0.0, 0, 700, 700, 0, 0, None))
+    c.append(("thr_dev", "thr_dev", 0.0, 2, 400, 400, 0, 0, (0.2, 0.9, 2.0)))
+    c.append(("border_removes_all", "small", 0.0, 10, 50, 50, 1, 1, None))
+    c.append(("big_d07-k20000", "big_d07", 0.0, 0, 20000, 20000, 1, 1, None))
+    c.append(("big_full-k32768", "big_full", 0.0, 0, 32768, 32768, 0, 0, None))
+    c.append(("big_ties-k32768", "big_ties", 0.0, 0, 32768, 32768, 1, 1, None))
+    return c
+
+
+SELECT_CASES = _select_cases()
+# many workgroups resident at once (hardware only)
+SELECT_OCCUPANCY_CASES = [(f"{m}-k{k}-s{sa}z{zf}", m, 0.0, 2, k, k, sa, zf, None)
+                          for m, k in (("occupancy128", 1000), ("occupancy16", 5000)) for sa, zf in ((0, 0), (1, 1))]
+
+
+def run_select_case(lib, case, device="cpu", runs=1):
+    _, name, thr, border, k, cap, sa, zf, thr_dev = case
+    return select_topk_case(lib, select_maps(name), thr, border, k, cap, sa, zf, thr_dev=thr_dev, device=device, runs=runs)
+
+
+def select_reused_workspace_results(lib, device="cpu", runs=1):
+    """One workspace and one set of output buffers through three calls: the dense map at k = 6000 (fills the two-chunk key table), the sparse map
+    at k = 6000 with sort_always and zero_fill (few keys: whatever the table held must not come back), the tie map at k = 300 (the one-workgroup
+    form after the chunked one)."""
+    H, W = select_maps("mixed").shape[1:]
+    bufs = SelectBuffers(lib, 1, H, W, 6000, 6000, device)
+    calls = (("mixed_dense", 6000, 0, 0), ("mixed_sparse", 6000, 1, 1), ("mixed_ties", 300, 0, 0))
+    return [select_topk_case(lib, select_maps(m), 0.0, 3, k, 6000, sa, zf, device=device, runs=runs, bufs=bufs) for m, k, sa, zf in calls]
+
+
+def select_error_case(lib, device="cpu"):
+    """zero_fill with k > H * W: an error return that names the size (torch.topk's 'selected index k out of range'); nothing is launched."""
+    _bind_selection(lib)
+    bf = SelectBuffers(lib, 1, 4, 5, 50, 64, device)
+    md = score_map(4, 5, 0)[None].to(device).contiguous()
+    rc = lib.dim_op_select_topk_f32(p(md), 1, 4, 5, 0.0, None, 0, 50, 64, 1, 1, p(bf.ws), p(bf.kp), p(bf.sc), p(bf.n), p(bf.nc), None)
+    _sync(device)
+    return rc, lib.dim_last_error().decode(), bf.cpu()
+
+
+# ---------------------------------------------------------------------------------------------------------------- descriptor sampling
+class SampleResult(NamedTuple):
+    out: torch.Tensor          # [batch][capacity][256] of the first run (CPU)
+    ref: torch.Tensor          # fp64 reference, rows past n_kpts[b] = SENTINEL
+    live: torch.Tensor         # [batch][capacity] bool: rows below n_kpts[b]
+    zero_rows: torch.Tensor    # [batch][capacity] bool: live keypoints whose four cells lie in the all-zero block
+    oracle_err: float          # max |oracle fp32 - fp64| over the live rows
+    guard_ok: bool
+    raws: tuple
+
+    @property
+    def repeatable(self):
+        return all(torch.equal(self.raws[0], r) for r in self.raws[1:])
+
+    @property
+    def err(self):
+        return (self.out.double() - self.ref)[self.live].abs().max().item() if bool(self.live.any()) else 0.0
+
+
+def _sample_coords64(k, h, w, fix_sampling):
+    """Input-pixel coordinates (ix, iy) in cell units of the integer keypoints k [N][2], in fp64, by the formulas of
+    oracle.superpoint_ref.sample_descriptors and grid_sample's un-normalisation of the branch's align_corners."""
+    k = k.double()
+    wh = torch.tensor([w, h], dtype=torch.float64)
+    if fix_sampling:
+        g = (k + 0.5) / (wh * 8) * 2 - 1
+        return g, ((g + 1) * wh - 1) / 2, False
+    g = (k - 4 + 0.5) / (wh * 8 - 4 - 0.5) * 2 - 1
+    return g, (g + 1) / 2 * (wh - 1), True
+
+
+@functools.lru_cache(maxsize=2)
+def _sample_inputs(h, w, batch, capacity, n_kpts, fix_sampling):
+    g = torch.Generator().manual_seed(h * 1000 + w + (7 if fix_sampling else 0))
+    dense = torch.randn(batch, h, w, 256, generator=g)
+    zy, zx = h // 2, w // 2                                   # the all-zero 2 x 2 block of cells
+    dense[:, zy:zy + 2, zx:zx + 2] = 0.0
+    Wp, Hp = 8 * w, 8 * h
+    if fix_sampling:   # ix = (kx + 0.5) / 8 - 0.5 = zx + 0.5
+        cx, cy = 8 * (zx + 1), 8 * (zy + 1)
+    else:              # ix = (kx - 3.5) / (8 w - 4.5) * (w - 1) = zx + 0.5
+        cx, cy = round(3.5 + (zx + 0.5) * (Wp - 4.5) / (w - 1)), round(3.5 + (zy + 0.5) * (Hp - 4.5) / (h - 1))
+    fixed = torch.tensor([(0, 0), (Wp - 1, 0), (0, Hp - 1), (Wp - 1, Hp - 1), (Wp // 2, 0), (Wp // 2, Hp - 1), (0, Hp // 2), (Wp - 1, Hp // 2),
+                          (cx, cy), (cx + 1, cy - 1)], dtype=torch.float32)
+    kp = torch.stack([torch.randint(0, Wp, (batch, capacity), generator=g), torch.randint(0, Hp, (batch, capacity), generator=g)], dim=2).float()
+    nf = min(len(fixed), capacity)
+    kp[:, :nf] = fixed[:nf]
+    n = torch.tensor(n_kpts, dtype=torch.int32)
+    live = torch.arange(capacity)[None, :] < n[:, None]
+    # fp64 reference and the fp32 oracle on the same inputs
+    dn64 = dense.double() / dense.double().norm(dim=3, keepdim=True).clamp_min(1e-12)
+    dn32 = F.normalize(dense.permute(0, 3, 1, 2), p=2, dim=1)
+    ref = torch.full((batch, capacity, 256), SENTINEL, dtype=torch.float64)
+    zero_rows = torch.zeros(batch, capacity, dtype=torch.bool)
+    oracle_err = 0.0
+    for b in range(batch):
+        m = int(n[b])
+        if m == 0:
+            continue
+        grid, ixy, ac = _sample_coords64(kp[b, :m], h, w, fix_sampling)
+        s = F.grid_sample(dn64[b].permute(2, 0, 1)[None], grid.view(1, 1, -1, 2), mode="bilinear", padding_mode="zeros", align_corners=ac)
+        r = F.normalize(s.reshape(256, m), p=2, dim=0, eps=1e-12).t()
+        ref[b, :m] = r
+        f = ixy.floor()
+        zero_rows[b, :m] = (f[:, 0] == zx) & (f[:, 1] == zy)
+        o32 = superpoint_ref.sample_descriptors(kp[b, :m], dn32[b][None], fix_sampling=bool(fix_sampling)).t()
+        oracle_err = max(oracle_err, (o32.double() - r).abs().max().item())
+    if min(n_kpts) >= nf >= 10:   # the two zero-block keypoints sit well inside the block (at least 0.05 cells from its cells' centres)
+        assert bool(zero_rows[:, 8:10].all())
+        assert not bool(ref[:, 8:10].any())
+    return dense, kp, n, ref, live, zero_rows, oracle_err
+
+
+def sample_descriptors_case(lib, h, w, batch, capacity, n_kpts, fix_sampling, device="cpu", runs=1):
+    """dim_op_sample_descriptors_f32 (sample_desc_kernel: one wave per keypoint) on an h x w x 256 randn cell map with an all-zero 2 x 2 block, at
+    the image's corners, edge midpoints, the zero block's centre and seeded random integer positions, vs fp64 (cells L2-normalised in fp64, the
+    coordinates of oracle.superpoint_ref.sample_descriptors in fp64, F.grid_sample in fp64, L2-normalised).  oracle_err: the error of the oracle
+    itself in fp32 on the same inputs — the yardstick of the kernel's error."""
+    _bind_selection(lib)
+    dense, kp, n, ref, live, zero_rows, oracle_err = _sample_inputs(h, w, batch, capacity, tuple(n_kpts), int(bool(fix_sampling)))
+    dd, kd, nd = dense.to(device).contiguous(), kp.to(device).contiguous(), n.to(device)
+    bufs = []
+    for _ in range(runs):
+        out = _dense_out(batch * capacity * 256, device)
+        assert lib.dim_op_sample_descriptors_f32(p(dd), p(kd), p(nd), p(out), batch, h, w, capacity, int(bool(fix_sampling)), None) == 0, lib.dim_last_error()
+        _sync(device)
+        bufs.append(out)
+    raws = tuple(b.cpu() for b in bufs)
+    numel = batch * capacity * 256
+    ok = all(bool((r[numel:] == SENTINEL).all()) for r in raws)
+    return SampleResult(raws[0][:numel].view(batch, capacity, 256), ref, live, zero_rows, oracle_err, ok, raws)
+
+
+def check_sample(r):
+    """Rows past n_kpts untouched, guard band untouched, zero-block keypoints exactly zero, every run the same bits, and the error within 4 x the
+    fp32 oracle's own (a different order of the same dozen roundings, not a different algorithm).  Returns (kernel error, oracle error)."""
+    print(f"sample_descriptors: kernel err {r.err:.4g} oracle fp32 err {r.oracle_err:.4g}")
+    assert r.guard_ok, "the guard band behind the descriptors was written"
+    assert bool((r.out[~r.live] == SENTINEL).all()), "rows at or past n_kpts were written"
+    assert r.repeatable, "two runs on the same inputs differ"
+    assert bool((r.out[r.zero_rows] == 0).all()), "a keypoint inside the all-zero block did not give an exactly zero descriptor"
+    assert r.err <= 4 * r.oracle_err, (r.err, r.oracle_err)
+    return r.err, r.oracle_err
+
+
+SAMPLE_CASES = [(5, 7, 3, 64, (0, 1, 64)), (12, 20, 2, 300, (300, 37))]       # (h, w, batch, capacity, n_kpts)
+SAMPLE_OCCUPANCY_CASE = (128, 128, 2, 2048, (2048, 2047))                       # cdiv(2048, 4) * 2 = 1024 workgroups (hardware only)

@@ -8,6 +8,7 @@ import torch
 
 from oracle import aliked_ref, lightglue_ref
 from tests import golden_cases as gc
+from tests import selection_mode_cases
 from tests.test_aliked_emu import compare_aliked
 
 pytestmark = pytest.mark.gpu
@@ -182,3 +183,20 @@ def test_aliked_trained_checkpoint_then_lightglue(hip_lib):
     ties = match_list_difference_is_a_tie(o["matches"][0, :S].cpu(), ref["matches"], ref["log_assignment"], 0.0, tie_tol=1e-4, ind0=ref["ind0"], ind1=ref["ind1"])
     assert len(ties) <= 2, ties
     _record({"test": "aliked_trained_then_lightglue", "kpts": [k0, k1], "matches": S, "ref_matches": int(ref["matches"].shape[0]), "ties": ties})
+
+
+# ---- DKD's non-default selection modes on hardware (the emulator runs the same bodies: tests/selection_mode_cases.py) ----
+def test_aliked_gpu_top_k_mode_vs_oracle(hip_lib):
+    selection_mode_cases.aliked_top_k_mode_vs_oracle(hip_lib, "cuda")
+
+
+def test_aliked_gpu_mean_threshold_mode_vs_oracle(hip_lib):
+    selection_mode_cases.aliked_mean_threshold_mode_vs_oracle(hip_lib, "cuda")
+
+
+def test_aliked_gpu_top_k_mode_fills_up_with_zero_score_pixels(hip_lib):
+    selection_mode_cases.aliked_top_k_mode_fills_up_with_zero_score_pixels(hip_lib, "cuda")
+
+
+def test_aliked_gpu_more_than_4096_keypoints(hip_lib):
+    selection_mode_cases.aliked_more_than_4096_keypoints(hip_lib, "cuda")

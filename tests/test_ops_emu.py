@@ -191,3 +191,30 @@ def test_lg_stage_features_equals_the_host_conversion(emu_lib, kf16, df16, dn):
         for i, n in enumerate((n0, n1)):
             assert np.array_equal(ktab[i, :n].numpy(), arrs[i][0]) and np.array_equal(dtab[i, :n].numpy(), arrs[i][1])
             assert not ktab[i, n:].any() and not dtab[i, n:].any()
+
+
+# ---------------------------------------------------------------------------------------------------------------- keypoint selection, descriptor sampling
+@pytest.mark.parametrize("case", op_cases.SELECT_CASES, ids=[c[0] for c in op_cases.SELECT_CASES])
+def test_select_topk_exact(emu_lib, case):
+    """dim_op_select_topk_f32 (count / scan / emit rows -> top-k -> zero fill of sp_post.hip) on crafted maps — ties at the k-th key, all scores
+    equal, n = k - 1 / k / k + 1, the 4096 hand-over, mixed batches, the largest tables — bit for bit against op_cases.select_topk_reference."""
+    op_cases.run_select_case(emu_lib, case).check()
+
+
+def test_select_topk_reused_workspace_carries_no_stale_keys(emu_lib):
+    for r in op_cases.select_reused_workspace_results(emu_lib):
+        r.check()
+
+
+def test_select_topk_zero_fill_beyond_the_map_is_an_error(emu_lib):
+    rc, msg, bufs = op_cases.select_error_case(emu_lib)
+    assert rc != 0 and "50" in msg and "4 x 5" in msg, (rc, msg)
+    assert all(bool((t == op_cases.SENTINEL).all()) for t in bufs)          # nothing ran (SENTINEL == I32_SENTINEL as a number)
+
+
+@pytest.mark.parametrize("fix_sampling", [0, 1])
+@pytest.mark.parametrize("h,w,batch,capacity,n_kpts", op_cases.SAMPLE_CASES)
+def test_sample_descriptors_vs_fp64(emu_lib, h, w, batch, capacity, n_kpts, fix_sampling):
+    """sample_desc_kernel at the corner cells, the edges, an all-zero block and random positions, within 4 x the fp32 oracle's own error against fp64
+    (op_cases.check_sample)."""
+    op_cases.check_sample(op_cases.sample_descriptors_case(emu_lib, h, w, batch, capacity, n_kpts, fix_sampling))

@@ -1,5 +1,6 @@
-"""GPU: the operator-level entry points (dim_op_* of include/dim_hip.h) of the matrix-core, convolution and NMS kernels ON HARDWARE against fp64 (NMS:
-bit-exact against the oracle), through the builders of tests/op_cases.py that the emulator tests use.
+"""GPU: the operator-level entry points (dim_op_* of include/dim_hip.h) of the matrix-core, convolution, NMS, keypoint-selection and descriptor-sampling
+kernels ON HARDWARE against fp64 (NMS and selection: bit-exact against the oracle / the stated rule), through the builders of tests/op_cases.py that the
+emulator tests use.
 
 The emulator has no memory model, no caches and no timing: workgroups run one after another and fibers in a fixed order between barriers.  A missing
 barrier around an LDS restage or a missing wait after an LDS-DMA is invisible there and shows on hardware only when two workgroups share a CU (the
@@ -39,6 +40,25 @@ Case -> kernel (from launch_gemm / launch_gemm_x6 / launch_gemm_x6_nt / launch_c
                                key 7 = 2 nms_kernel<1,64,1024,8> / <3,64,1024,10> / <4,64,1024,12>
   test_nms_large_map           4 x 500 x 500, 8 * 8 * 4 = 256 tiles: the 64-tile kernels by themselves under key 7 = 1, the 32-tile ones under key 7 = 0
 
+  test_select_topk (sp_post.hip; per image: count_rows / emit_rows cdiv(H,4) wg of 4 waves, scan_rows 1 wg, topk_zero_fill 1 wg; the top-k form below)
+    equal  1x72x100, k 300 / 4096             topk_kernel, the radix select walks all 8 key bytes                      1 wg
+                     k 4097 / 5000            topk_select_big -> topk_chunk_sort -> topk_merge                         1 + 2 + 32 wg
+    ties   1x100x132 (6 levels), k 1000 / 4096            topk_kernel, k-th key inside a tie group                     1 wg
+                     k 4097 / 8192 / 8193     the chunked form, 2 / 2 / 3 chunks                                       1 + 2|3 + 32|48 wg
+    n_near_k 1x96x128, k = n-1, n, n+1        topk_kernel: select / keep-all / sort-everything (+ zero fill of 1)      1 wg
+    handover 1x80x100, k 4095 / 4096 / 4097   topk_kernel | the chunked form, n ~ 4800                                 1 | 1 + 2 + 32 wg
+    mixed  5x90x124 (empty, sparse, dense, 4 levels, one pixel), k 500 / 4096 / 6000     per-image early returns       5 | 5 + 10 + 160 wg
+    keep_all 2x50x70, k -1, capacity 1000 / 4096          topk_keep_all, truncated and not                             2 wg
+    wide1300 / wide1301 / w260                count_rows / emit_rows: float4 loop second step, scalar loop, 2nd group  2 / 2 / 20 wg
+    tall   2x1030x8                           scan_rows_kernel with two rows per thread                                258 x 2 / 2 wg
+    thr_dev 3x60x84                           per-image device thresholds 0.2 / 0.9 / 2.0                              15 x 3 wg
+    border_removes_all 1x20x30                topk_zero_fill fills all of k = 50                                       1 wg
+    big    1x200x200, k 20000 / 32768         the chunked form at 5 / 8 chunks                                         1 + 5|8 + 80|128 wg
+    occupancy 128x64x96 k 1000                topk_kernel x 128, count / emit 16 x 128 = 2048 wg, zero_fill 128 wg
+              16x100x132 k 5000               the chunked form: 16 + 2 x 16 + 32 x 16 = 560 wg, count / emit 25 x 16 wg
+  test_select_topk_reused_workspace           three calls on one workspace: chunked (2 chunks) -> chunked, sparse + fill -> topk_kernel
+  test_sample_descriptors                     sample_desc_kernel, one wave per keypoint: 5x7 (16 x 3 wg), 12x20 (75 x 2 wg), 128x128 (512 x 2 = 1024 wg)
+
 launch_gemm_x6's gemm_x6_kernel<2,64,2,2> branch is not in the table: a small problem has cdiv(M,128) * cdiv(N,128) < 256 workgroups, so at most
 2 * 255 = 510 workgroups of 64 rows, which is never above the 512 that the branch before it accepts.
 """
@@ -48,6 +68,7 @@ import pytest
 import torch
 
 from tests import op_cases
+from tests.test_aliked_gpu import _record   # appends one JSON line to the measured-parity log
 
 pytestmark = pytest.mark.gpu
 
@@ -191,3 +212,36 @@ def test_nms_large_map(hip_lib, radius):
     assert r.repeatable and r.guard_ok and o.repeatable and o.guard_ok
     assert torch.equal(r.out, r.ref) and torch.equal(o.out, r.ref)
     assert 0 < int((r.ref > 0).sum()) < r.ref.numel() // 2
+
+
+# ---------------------------------------------------------------------------------------------------------------- keypoint selection
+ALL_SELECT = op_cases.SELECT_CASES + op_cases.SELECT_OCCUPANCY_CASES
+
+
+@pytest.mark.parametrize("case", ALL_SELECT, ids=[c[0] for c in ALL_SELECT])
+def test_select_topk(hip_lib, case):
+    """Counts, coordinates, score bits, rows past n_out, guard bands and run-to-run bits: all exact (op_cases.SelectResult.check).  On hardware
+    the gather's atomics fall in any order and many workgroups run at once; the result must not depend on either."""
+    op_cases.run_select_case(hip_lib, case, device=DEV, runs=2).check()
+
+
+def test_select_topk_reused_workspace(hip_lib):
+    for r in op_cases.select_reused_workspace_results(hip_lib, device=DEV, runs=2):
+        r.check()
+
+
+def test_select_topk_zero_fill_beyond_the_map_is_an_error(hip_lib):
+    rc, msg, bufs = op_cases.select_error_case(hip_lib, device=DEV)
+    assert rc != 0 and "50" in msg and "4 x 5" in msg, (rc, msg)
+    assert all(bool((t == op_cases.SENTINEL).all()) for t in bufs)
+
+
+# ---------------------------------------------------------------------------------------------------------------- descriptor sampling
+@pytest.mark.parametrize("fix_sampling", [0, 1])
+@pytest.mark.parametrize("h,w,batch,capacity,n_kpts", op_cases.SAMPLE_CASES + [op_cases.SAMPLE_OCCUPANCY_CASE])
+def test_sample_descriptors(hip_lib, h, w, batch, capacity, n_kpts, fix_sampling):
+    """Within 4 x the fp32 oracle's own error against fp64; the measured pairs are in profiles/sp_post_ops_parity.json."""
+    r = op_cases.sample_descriptors_case(hip_lib, h, w, batch, capacity, n_kpts, fix_sampling, device=DEV, runs=2)
+    _record({"case": f"sample_descriptors {h}x{w} cells, batch {batch} x {capacity}, fix_sampling {fix_sampling}", "kernel_err": r.err,
+             "oracle_fp32_err": r.oracle_err})
+    op_cases.check_sample(r)

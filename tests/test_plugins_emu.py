@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import lightglue_ref, superpoint_ref
+from tests import selection_mode_cases
 
 plugins = importlib.import_module("deep-image-matching_amd.plugins")
 weights = importlib.import_module("deep-image-matching_amd.weights")
@@ -149,20 +150,7 @@ def test_plugins_load_checkpoint_files(emu_install, tmp_path):
 
 
 def test_keep_all_mode_never_drops_keypoints(emu_install):
-    """with max_keypoints = -1 an image with more candidates than the slot is re-extracted with a larger
-    slot, so every keypoint the reference returns is returned."""
-    cfg = {"general": {}, "extractor": {"name": "superpoint", "nms_radius": 1, "keypoint_threshold": 0.0, "max_keypoints": -1,
-                                        "remove_borders": 1, "allow_synthetic_weights": True}}
-    ex = plugins.SuperPointExtractor(cfg)
-    img = (torch.rand(48, 64, generator=torch.Generator().manual_seed(9)) * 255).numpy().astype(np.float32)
-    ex._ensure(48, 64)
-    ex._net = None
-    ex._capacity = lambda H, W: max(ex._min_capacity, 64)   # force a slot that is too small for the first call
-    f = ex._extract(img)
-    ref = superpoint_ref.superpoint_forward(torch.tensor(img / 255.0, dtype=torch.float)[None, None], ex._sd, ex._net_cfg)
-    assert ref["keypoints"].shape[0] > 64
-    assert f["keypoints"].shape[0] == ref["keypoints"].shape[0]
-    assert np.array_equal(f["keypoints"], ref["keypoints"].numpy())  # row-major order, like torch.nonzero
+    selection_mode_cases.keep_all_mode_never_drops_keypoints(emu_install, "cpu")
 
 
 def test_arithmetic_is_a_per_handle_choice(emu_install):

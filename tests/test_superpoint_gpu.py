@@ -8,6 +8,7 @@ import torch
 
 from oracle import superpoint_ref
 from tests import golden_cases as gc
+from tests import selection_mode_cases
 from tests.parity import compare_superpoint, order_is_reference_like
 
 pytestmark = pytest.mark.gpu
@@ -127,3 +128,8 @@ def test_winograd_conv1b_variant_vs_direct_and_oracle(hip_research_lib):
             assert res["n_out"] == 2048
     finally:
         hip_lib.dim_tune_set(15, 0)
+
+
+def test_superpoint_gpu_keep_all_mode_never_drops_keypoints(hip_lib):
+    """The plugin's keep-all regrow on hardware (the emulator runs the same body: tests/selection_mode_cases.py)."""
+    selection_mode_cases.keep_all_mode_never_drops_keypoints(hip_lib, "cuda")
