@@ -24,6 +24,7 @@ import torch
 
 from . import capi
 from . import weights as _weights
+from .alike_hip import AlikeHIP
 from .aliked_hip import AlikedHIP
 from .lightglue_hip import LightGlueHIP
 from .nn_hip import NearestNeighborHIP, check_mode as _check_nn_mode
@@ -334,6 +335,64 @@ class AlikedExtractor(BatchedTilingMixin, _ExtractorBase):
         return _to_device(self, _frame2array(image), device, sync=True)
 
 
+class AlikeExtractor(_ExtractorBase):
+    """extractors/alike.py:8 — ALIKE (alike-t / s / n / l) on the gfx950 library: eval-mode BatchNorm, sub-pixel keypoints, scores = the score map
+    sampled at the refined positions, descriptors sampled bilinearly from a descriptor map that is only ever evaluated around the keypoints."""
+
+    _default_conf = {  # AKX:9-17 (the "name:" key with the stray colon is the reference's)
+        "name:": "alike",
+        "model": "alike-s",
+        "device": "cuda",
+        "top_k": 15000,
+        "scores_th": 0.2,
+        "n_limit": 15000,
+        "subpixel": True,
+    }
+    required_inputs = []
+    grayscale = False
+    descriptor_size = 96
+
+    def __init__(self, config):
+        super().__init__(config)
+        self._lib = capi.load()
+        self._device = _resolve_device(self._device, "AlikeExtractor")
+        cfg = self.config.get("extractor")
+        if cfg["model"] not in _weights.ALIKE_CFGS:
+            raise ValueError(f"AlikeExtractor: unknown model {cfg['model']!r}; expected one of {sorted(_weights.ALIKE_CFGS)}")
+        # the reference always extracts with sub_pixel=True (AKX:39), whatever the "subpixel" key says
+        self._net_cfg = {"model": cfg["model"], "top_k": int(cfg["top_k"]), "scores_th": float(cfg["scores_th"]), "n_limit": int(cfg["n_limit"])}
+        arith = _apply_arithmetic(cfg, self._lib)
+        if arith is not None:
+            self._net_cfg["arithmetic"] = arith
+        self._net_cfg["on_saturation"] = _saturation_policy(cfg)
+        path = cfg.get("weights_path") or os.environ.get("DIM_ALIKE_WEIGHTS")
+        if path is None and cfg.get("allow_synthetic_weights"):
+            logger.warning("ALIKE: running on seeded SYNTHETIC weights (allow_synthetic_weights) - test / benchmark use only")
+        self._sd = _weights.load_alike_state_dict(path, cfg["model"], allow_synthetic=bool(cfg.get("allow_synthetic_weights", False)))
+        self.descriptor_size = int(_weights.ALIKE_CFGS[cfg["model"]][4])   # 64 / 96 / 128 / 128 (the reference's class attribute says 96 for all)
+        self._net: Optional[AlikeHIP] = None
+        self._net_hw = (0, 0)
+
+    def _ensure(self, H: int, W: int):
+        if self._net is None or H > self._net_hw[0] or W > self._net_hw[1]:
+            hw = (max(H, self._net_hw[0]), max(W, self._net_hw[1]))
+            self._net = AlikeHIP(self._sd, self._net_cfg, max_batch=1, max_hw=hw, device=self._device, lib=self._lib)
+            self._net_hw = hw
+
+    @torch.no_grad()
+    def _extract(self, image: np.ndarray) -> dict:
+        """image: HxWx3 RGB, 0..255 (uint8 as the reference's loader hands it over, or float).  Returns numpy keypoints (N,2), descriptors (D,N)
+        (AKX:42 transposes), scores (N,)."""
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise AssertionError("input image shape should be [HxWx3]")   # AKM:143-144
+        self._ensure(image.shape[0], image.shape[1])
+        return _features_to_numpy(self, self._net.extract_batch_guarded(_to_device(self, image, self._device)[None].contiguous()))
+
+    def _frame2tensor(self, image: np.ndarray, device: str = "cuda"):
+        """AKX:46-54: the reference's hook is empty (ALike.forward converts the array itself)."""
+        return None
+
+
 def featuresDict2Lightglue(feats: dict) -> dict:
     """matchers/lightglue.py:8-66 up to (not including) the tensor conversion: unwrap, fix the
     descriptor layout by the keypoint count ((D,N) -> (N,D)), drop path keys."""
@@ -619,9 +678,20 @@ class KorniaMatcher(_ResidentMatcherMixin, BatchedTileMatchingMixin, _MatcherBas
                 return d.T, 0, d.shape[0], d.shape[1]          # the (N, D) array behind a transposed view
             return np.ascontiguousarray(d), 1, d.shape[0], d.shape[1]
 
-        (d0, dn0, D0, m), (d1, dn1, D1, n) = raw(feats0), raw(feats1)
+        def widen(r):
+            """The matcher's k-steps need a width that is a multiple of 64: any other width (ALIKE-s: 96) gets zero columns up to the next
+            multiple, which leave every distance and ratio as they were (the device-side route to the same table is dim_alike_config.desc_stride)"""
+            d, dn, D, cnt = r
+            if D % 64 == 0 or D == 0:
+                return r
+            nd = d.T if dn else d                                   # (N, D)
+            wide = np.zeros((nd.shape[0], (D + 63) // 64 * 64), dtype=nd.dtype)
+            wide[:, :D] = nd
+            return wide, 0, wide.shape[1], cnt
+
+        (d0, dn0, D0, m), (d1, dn1, D1, n) = widen(raw(feats0)), widen(raw(feats1))
         if D0 != D1 or D0 % 64 != 0:
-            raise ValueError(f"descriptor dimensions {D0} / {D1}: both images need the same width, a multiple of 64")
+            raise ValueError(f"descriptor dimensions {D0} / {D1}: both images need the same width")
         D = D0
         self._set_dim(D)
         self._ensure(max(m, n))

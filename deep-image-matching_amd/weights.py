@@ -224,3 +224,84 @@ def load_aliked_state_dict(path: str | None = None, seed: int = 7, model_name: s
         return synthetic_aliked_state_dict(seed, model_name)
     sd = torch.load(str(Path(path)), map_location="cpu")
     return {k: (v.float().contiguous() if v.is_floating_point() else v) for k, v in sd.items()}
+
+
+ALIKE_CFGS = {  # thirdparty/alike/alike.py:15-56  c1, c2, c3, c4, dim, single_head, radius
+    "alike-t": (8, 16, 32, 64, 64, 1, 2),
+    "alike-s": (8, 16, 48, 96, 96, 1, 2),
+    "alike-n": (16, 32, 64, 128, 128, 1, 2),
+    "alike-l": (32, 64, 128, 128, 128, 0, 2),
+}
+ALIKE_BN = ["block1.bn1", "block1.bn2", "block2.bn1", "block2.bn2", "block3.bn1", "block3.bn2", "block4.bn1", "block4.bn2"]
+
+
+def alike_state_dict_shapes(model: str) -> Dict[str, tuple]:
+    """Every tensor of an ALIKE checkpoint and its shape, derived from the model's geometry row (alnet.py:104-153)."""
+    if model not in ALIKE_CFGS:
+        raise ValueError(f"unknown ALIKE model {model!r}; expected one of {sorted(ALIKE_CFGS)}")
+    c1, c2, c3, c4, dim, single_head, _ = ALIKE_CFGS[model]
+    t: Dict[str, tuple] = {}
+    for blk, ci, co in (("block1", 3, c1), ("block2", c1, c2), ("block3", c2, c3), ("block4", c3, c4)):
+        t[blk + ".conv1.weight"] = (co, ci, 3, 3)
+        t[blk + ".conv2.weight"] = (co, co, 3, 3)
+        for bn in ("bn1", "bn2"):
+            for leaf in ("weight", "bias", "running_mean", "running_var"):
+                t[f"{blk}.{bn}.{leaf}"] = (co,)
+            t[f"{blk}.{bn}.num_batches_tracked"] = ()
+        if blk != "block1":
+            t[blk + ".downsample.weight"] = (co, ci, 1, 1)
+            t[blk + ".downsample.bias"] = (co,)
+    # conv4 is declared conv1x1(dim, dim // 4) (alnet.py:135) and applied to block4's c4 channels: every shipped row has c4 == dim
+    for name, ci in (("conv1", c1), ("conv2", c2), ("conv3", c3), ("conv4", dim)):
+        t[name + ".weight"] = (dim // 4, ci, 1, 1)
+    if not single_head:
+        t["convhead1.weight"] = (dim, dim, 1, 1)
+    t["convhead2.weight"] = (dim + 1, dim, 1, 1)
+    return t
+
+
+def validate_alike_state_dict(sd: Dict[str, torch.Tensor], model: str) -> None:
+    """KeyError for a missing / unexpected tensor, ValueError for a wrong shape — each naming the tensor — before anything native is called."""
+    table = alike_state_dict_shapes(model)
+    for k, shape in table.items():
+        if k not in sd:
+            if k.endswith("num_batches_tracked"):
+                continue
+            raise KeyError(f"ALIKE {model}: state dict has no tensor {k!r}")
+        if tuple(sd[k].shape) != tuple(shape):
+            raise ValueError(f"ALIKE {model}: tensor {k!r} has shape {tuple(sd[k].shape)}, expected {tuple(shape)}")
+    for k in sd:
+        if k not in table:
+            raise KeyError(f"ALIKE {model}: unexpected tensor {k!r} in the state dict")
+
+
+def synthetic_alike_state_dict(seed: int = 11, model: str = "alike-n") -> Dict[str, torch.Tensor]:
+    """Seeded synthetic ALIKE weights in the checkpoint layout (running statistics included: BatchNorm runs in eval mode)."""
+    g = torch.Generator().manual_seed(seed)
+    sd: Dict[str, torch.Tensor] = {}
+    for k, shape in alike_state_dict_shapes(model).items():
+        if k.endswith("num_batches_tracked"):
+            sd[k] = torch.tensor(0)
+        elif k.endswith("running_var"):
+            sd[k] = 0.5 + torch.rand(shape, generator=g)
+        elif k.endswith("running_mean") or k.endswith(".bias"):
+            sd[k] = 0.1 * torch.randn(shape, generator=g)
+        elif len(shape) == 1:
+            sd[k] = 1.0 + 0.1 * torch.randn(shape, generator=g)
+        else:
+            sd[k] = torch.randn(shape, generator=g) * math.sqrt(2.0 / (shape[1] * shape[2] * shape[3]))
+    return sd
+
+
+def load_alike_state_dict(path: str | None = None, model: str = "alike-s", seed: int = 11, allow_synthetic: bool = False) -> Dict[str, torch.Tensor]:
+    """thirdparty/alike/models/alike-{t,s,n,l}.pth (a plain state dict; alike.py:90-92), validated against the model's geometry.
+    ``path``: a file name, or an open binary file holding the same bytes (the tests join the checkpoint from slices in memory)."""
+    if model not in ALIKE_CFGS:
+        raise ValueError(f"unknown ALIKE model {model!r}; expected one of {sorted(ALIKE_CFGS)}")
+    if path is None:
+        _no_weights("ALIKE (thirdparty/alike/models/alike-*.pth in the reference tree)", "DIM_ALIKE_WEIGHTS", allow_synthetic)
+        return synthetic_alike_state_dict(seed, model)
+    sd = torch.load(path if hasattr(path, "read") else str(Path(path)), map_location="cpu")   # (a path or an open binary file)
+    sd = {k: (v.float().contiguous() if v.is_floating_point() else v) for k, v in sd.items()}
+    validate_alike_state_dict(sd, model)
+    return sd

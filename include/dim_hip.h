@@ -98,6 +98,7 @@ enum {
   DIM_SAT_LG_DESC,        /* residual stream after ffn.3 */
   DIM_SAT_OP,             /* operator-level entry points (dim_op_*_x6) */
   DIM_SAT_ALIKED,         /* ALIKED: inputs of the split-precision convolutions / GEMMs (image, BatchNorm+SELU outputs, SDDH samples) */
+  DIM_SAT_ALIKE,          /* ALIKE: activations stored by the encoder / aggregation convolutions, rows and outputs of the head products */
   DIM_SAT_SITES = 16
 };
 int dim_saturation_read(unsigned* counts_host, unsigned long long* total, int reset, void* stream);
@@ -208,6 +209,48 @@ int dim_aliked_extract(dim_aliked* h, const float* images_dev, int batch, int H,
                        float* scores_dev, float* desc_dev, int32_t* n_kpts_dev, void* stream);
 /* Parity taps: un-normalised feature map [batch][Hp][Wp][dim] in the padded frame, score map [batch][H][W]. */
 int dim_aliked_debug_buffers(dim_aliked* h, const float** x1234, const float** score_map, int* hp, int* wp, int* pad_t, int* pad_l);
+
+/* ------------------------------------------------------------------------ */
+/* ALIKE (reference AKN = thirdparty/alike/alnet.py, AKM = thirdparty/alike/alike.py, AKD =
+ * thirdparty/alike/soft_detect.py, driven by extractors/alike.py:22-44)     */
+/* ------------------------------------------------------------------------ */
+
+/* Learnable tensors and BatchNorm running statistics in the reference's state_dict layout (conv weights OIHW, host pointers).
+ * BatchNorm runs in EVAL mode (AKM:90-94 calls .eval() when a checkpoint is loaded — unlike ALIKED's quirk Q7): it is folded into
+ * a per-channel scale and bias at create time (eps 1e-5). */
+typedef struct dim_alike_weights {
+  const float *block1_conv1, *block1_conv2, *block2_conv1, *block2_conv2;   /* (c1,3,3,3), (c1,c1,3,3), (c2,c1,3,3), (c2,c2,3,3) */
+  const float *block3_conv1, *block3_conv2, *block4_conv1, *block4_conv2;   /* (c3,c2,3,3), (c3,c3,3,3), (c4,c3,3,3), (c4,c4,3,3) */
+  const float *bn_weight[8], *bn_bias[8], *bn_mean[8], *bn_var[8];          /* block1.bn1, block1.bn2, block2.bn1, ..., block4.bn2 */
+  const float *block2_ds_w, *block2_ds_b, *block3_ds_w, *block3_ds_b, *block4_ds_w, *block4_ds_b;   /* blockN.downsample (1x1, with bias; AKN:110,118,126) */
+  const float *conv1, *conv2, *conv3, *conv4;   /* (dim/4, c, 1, 1), bias-free (AKN:132-135) */
+  const float *convhead1;                        /* (dim, dim, 1, 1); NULL for single-head models (AKN:151-152) */
+  const float *convhead2;                        /* (dim + 1, dim, 1, 1) (AKN:153): rows [0, dim) = descriptor head, row dim = score */
+} dim_alike_weights;
+
+/* One row of AKM:15-56 + the DKD arguments of extractors/alike.py:28-34. */
+typedef struct dim_alike_config {
+  int c1, c2, c3, c4, dim, single_head;   /* alike-t 8,16,32,64,64,1; alike-s 8,16,48,96,96,1; alike-n 16,32,64,128,128,1; alike-l 32,64,128,128,128,0 */
+  int radius;                             /* 2 in every row (soft-argmax window AKD:89; the NMS radius is 2 regardless, AKD:102) */
+  int top_k;                              /* > 0: the top_k highest NMS maxima, score-descending, zero-score pixels (the first non-candidates in row-major
+                                             order) filling up (AKD:111-113); <= 0: threshold mode */
+  double scores_th;                       /* threshold mode: maxima > scores_th; the image's mean score when <= 0 or when nothing passes (AKD:115-122) */
+  int n_limit;                            /* threshold mode: row-major order, or the n_limit highest, score-descending, when more survive (AKD:128-133) */
+  int desc_stride;                        /* floats per descriptor row: >= dim, <= 128, multiple of 4, 0 = dim; columns [dim, desc_stride) are written as zeros */
+} dim_alike_config;
+
+typedef struct dim_alike dim_alike;
+/* capacity (<= 32768) must cover top_k (top-k mode) or n_limit (threshold mode); max_batch <= 64; max_h, max_w >= 16. */
+int dim_alike_create(const dim_alike_weights* w, const dim_alike_config* cfg, int max_batch, int max_h, int max_w, int capacity, dim_alike** out);
+void dim_alike_destroy(dim_alike* h);
+/* images_dev: [batch][H][W][3] fp32 RGB, already /255 (AKM:154).  The network runs on the frame zero-padded at the bottom and right to
+ * multiples of 32 (AKM:105-113); the maps are cropped back to H x W (AKM:119-121).
+ * kpts (x, y): soft-argmax refined pixel coordinates (AKD:139-178, AKM:163); scores: the score map sampled bilinearly there (AKD:180-187);
+ * desc: [batch][capacity][desc_stride], the bilinearly sampled, twice L2-normalised descriptors (AKM:125, AKD:55-69); rows at or past n_kpts are not written. */
+int dim_alike_extract(dim_alike* h, const float* images_dev, int batch, int H, int W, float* kpts_xy_dev, float* scores_dev, float* desc_dev,
+                      int32_t* n_kpts_dev, void* stream);
+/* Parity taps of the last call: score map [batch][H][W], border-cleared NMS map [batch][H][W] (AKD:102-108), padded frame sizes. */
+int dim_alike_debug_buffers(dim_alike* h, const float** score_map, const float** nms_map, int* hp, int* wp);
 
 /* ------------------------------------------------------------------------ */
 /* LightGlue (reference LGN:300-610)                                        */
