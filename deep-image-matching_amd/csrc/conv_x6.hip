@@ -53,7 +53,14 @@ constexpr int w_slice(int npl) { return npl * 3 * 2 * 64 * 8; }              // 
 //     a double-buffered Wp while the MFMAs of the current row run: no staging registers, no ds_write pass, one barrier per
 //     kernel row instead of two (the slice copy through registers was the largest staging cost: +4 % of the step when
 //     switched off in the stage-ablation experiment).
-template <int CIN, int POOL, int PF, bool F1A, int MODE, bool PIN, bool POUT, int MR = 2, bool WDMA = false>
+// BN (the open SuperPoint: conv -> ReLU -> BatchNorm(eval) -> pool): the epilogue is y = s[co] * relu(acc * inv + b[co]) + t[co] with the
+//     per-channel s | t stored behind the bias (bias[cout + co], bias[2 cout + co]); `relu` is not consulted.  The activations are SIGNED:
+//     pre-split outputs clamp to +-65504 and the range guard tracks |y|.  The pooled form takes the max AND the min of the 2x2 group of raw
+//     accumulators and keeps the max where s >= 0, the min otherwise: relu and the positive factor inv are monotone, so that value's y is
+//     the largest of the four = max_pool(bn(relu(x))) for either sign of s.  With F1A conv1a's own s | t (b1a[64 + c], b1a[128 + c]) follow
+//     its ReLU for pixels inside the image; conv1b's zero padding stays zero.  A compile-time flag: every BN = false instantiation is the
+//     code it was.
+template <int CIN, int POOL, int PF, bool F1A, int MODE, bool PIN, bool POUT, int MR = 2, bool WDMA = false, bool BN = false>
 __global__ __launch_bounds__(256, ((PF == 2 || MR == 4) ? 2 : 3)) void conv3x3_x6_kernel(const float* __restrict__ in, const unsigned short* __restrict__ wx,
                                                             const float* __restrict__ bias, float* __restrict__ out, int H, int W,
                                                             int cout, int relu, int tiles_x, const float* __restrict__ w1a,
@@ -69,7 +76,7 @@ __global__ __launch_bounds__(256, ((PF == 2 || MR == 4) ? 2 : 3)) void conv3x3_x
   __shared__ u32x4 Wp[(WDMA ? 2 : 1) * WSL];
   constexpr int IMW = IW + 2, IMH = IH + 2;  // image tile of the fused conv1a: halo of the halo
   __shared__ float Img[F1A ? IMH * IMW : 1];
-  __shared__ float W1a[F1A ? 9 * 64 + 64 : 1];  // conv1a weights [tap][64] + bias[64]: read per chunk from LDS, not from L2
+  __shared__ float W1a[F1A ? 9 * 64 + 64 + (BN ? 128 : 0) : 1];  // conv1a weights [tap][64] + bias[64] (+ BN: s[64], t[64]): read per chunk from LDS, not from L2
   constexpr int NCHUNK = CIN / 16;
 
   const int t = threadIdx.x;
@@ -172,6 +179,8 @@ __global__ __launch_bounds__(256, ((PF == 2 || MR == 4) ? 2 : 3)) void conv3x3_x
       wr[k][0] = v.x; wr[k][1] = v.y; wr[k][2] = v.z; wr[k][3] = v.w;
     }
     const float4 bv = *(const float4*)&W1a[9 * 64 + c * 16 + q * 4];
+    float4 sv = make_float4(1.f, 1.f, 1.f, 1.f), tv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (BN) { sv = *(const float4*)&W1a[10 * 64 + c * 16 + q * 4]; tv = *(const float4*)&W1a[11 * 64 + c * 16 + q * 4]; }
 #pragma unroll
     for (int i = 0; i < NIN; ++i) {
       const int io = img_off[i];  // -1: not a halo pixel of this tile, or outside the image (conv1b's zero padding)
@@ -183,6 +192,11 @@ __global__ __launch_bounds__(256, ((PF == 2 || MR == 4) ? 2 : 3)) void conv3x3_x
         o0 = fmaf(v, wr[k][0], o0); o1 = fmaf(v, wr[k][1], o1);
         o2 = fmaf(v, wr[k][2], o2); o3 = fmaf(v, wr[k][3], o3);
       }
+      if (BN)  // conv1a's BatchNorm after its ReLU, inside the image only (t is pre-multiplied by the activation scale like the bias, s is not)
+        rin[i] = io >= 0 ? make_float4(fmaf(sv.x, fmaxf(o0 + bv.x, 0.f), tv.x), fmaf(sv.y, fmaxf(o1 + bv.y, 0.f), tv.y),
+                                       fmaf(sv.z, fmaxf(o2 + bv.z, 0.f), tv.z), fmaf(sv.w, fmaxf(o3 + bv.w, 0.f), tv.w))
+                         : make_float4(0.f, 0.f, 0.f, 0.f);
+      else
       rin[i] = io >= 0 ? make_float4(fmaxf(o0 + bv.x, 0.f), fmaxf(o1 + bv.y, 0.f), fmaxf(o2 + bv.z, 0.f), fmaxf(o3 + bv.w, 0.f))
                        : make_float4(0.f, 0.f, 0.f, 0.f);
     }
@@ -202,6 +216,7 @@ __global__ __launch_bounds__(256, ((PF == 2 || MR == 4) ? 2 : 3)) void conv3x3_x
     // weights and bias pre-multiplied by the activation scale (a power of two: fmaf(v, s w, s acc) = s fmaf(v, w, acc)
     // exactly), so the conv1a outputs come out scaled and their split skips the multiply
     for (int idx = t; idx < 9 * 64 + 64; idx += 256) W1a[idx] = (idx < 9 * 64 ? w1a[idx] : b1a[idx - 9 * 64]) * S::act_scale();
+    if (BN && t < 128) W1a[10 * 64 + t] = b1a[64 + t] * (t < 64 ? 1.0f : S::act_scale());   // s as it is, t scaled
   }
 
   // WDMA: slice `ph` = (chunk, kernel row) of this cout block, the slices are contiguous in HBM; wave w moves items
@@ -304,10 +319,20 @@ __global__ __launch_bounds__(256, ((PF == 2 || MR == 4) ? 2 : 3)) void conv3x3_x
       const int co = cb * 64 + n * 32 + lx;
       const float bv = bias[co] * OSC;
       const float inv_scale = inv_ch[co] * OSC;
+      float sv = 1.0f, tv = 0.0f;
+      if (BN) { sv = bias[cout + co]; tv = bias[2 * cout + co] * OSC; }
       const unsigned c2 = (unsigned)(co - par);  // the even channel of this lane pair
       const unsigned cpart = ((c2 >> 4) * 64u + (c2 & 15u)) * 2u;
       auto finish = [&](float& v0, float& v1) {  // activation, range guard, clamp
-        if (POUT) {
+        if (BN) {   // signed results: guard |y|, clamp both ways
+          v0 = fmaf(sv, fmaxf(v0, 0.0f), tv);
+          v1 = fmaf(sv, fmaxf(v1, 0.0f), tv);
+          vmax = sat_track(vmax, v0, v1);
+          if (POUT) {
+            v0 = __builtin_amdgcn_fmed3f(v0, -65504.0f, 65504.0f);
+            v1 = __builtin_amdgcn_fmed3f(v1, -65504.0f, 65504.0f);
+          }
+        } else if (POUT) {
           vmax = fmaxf(vmax, fmaxf(v0, v1));
           v0 = __builtin_amdgcn_fmed3f(v0, 0.0f, 65504.0f);
           v1 = __builtin_amdgcn_fmed3f(v1, 0.0f, 65504.0f);
@@ -323,6 +348,11 @@ __global__ __launch_bounds__(256, ((PF == 2 || MR == 4) ? 2 : 3)) void conv3x3_x
           float pv[8];
 #pragma unroll
           for (int r = 0; r < 16; r += 2)
+            if (BN) {
+              const float mx = fmaxf(fmaxf(acc[2 * mp][n][r], acc[2 * mp][n][r + 1]), fmaxf(acc[2 * mp + 1][n][r], acc[2 * mp + 1][n][r + 1]));
+              const float mn = fminf(fminf(acc[2 * mp][n][r], acc[2 * mp][n][r + 1]), fminf(acc[2 * mp + 1][n][r], acc[2 * mp + 1][n][r + 1]));
+              pv[r >> 1] = (sv >= 0.0f ? mx : mn) * inv_scale + bv;
+            } else
             pv[r >> 1] = fmaxf(fmaxf(acc[2 * mp][n][r], acc[2 * mp][n][r + 1]), fmaxf(acc[2 * mp + 1][n][r], acc[2 * mp + 1][n][r + 1])) * inv_scale + bv;
 #pragma unroll
           for (int j = 0; j < 8; j += 2) {
@@ -422,7 +452,7 @@ int dim_conv_x6_variant() { return g_conv_x6_variant; }
 void dim_conv_x6_set_variant(int v) { g_conv_x6_variant = v; }
 
 int launch_conv3x3_x6(const float* in, const SplitWeights& wt, const float* bias, float* out, int batch, int H, int W, int cin,
-                      int cout, int pool, int relu, hipStream_t s, unsigned* sat) {
+                      int cout, int pool, int relu, hipStream_t s, unsigned* sat, int bn) {
   DIM_REQUIRE(cout % 64 == 0, "conv3x3_x6: cout=%d must be a multiple of 64", cout);
   DIM_REQUIRE(cin == 64 || cin == 128, "conv3x3_x6: cin=%d unsupported (64 or 128)", cin);
   DIM_REQUIRE(wt.dev && (wt.mode == 1 || wt.mode == 2), "conv3x3_x6: weights not prepared (mode %d)", wt.mode);
@@ -431,15 +461,18 @@ int launch_conv3x3_x6(const float* in, const SplitWeights& wt, const float* bias
   dim3 grid(tiles_x * tiles_y, cout / 64, batch);
   const unsigned short* wx = wt.dev;
   const float* inv = wt.inv_ch();
-#define DIM_CONV6(CI, P, PFV, MD) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_x6_kernel<CI, P, PFV, false, MD, false, false>), grid, dim3(256), 0, s, in, wx, bias, out, H, W, cout, relu, tiles_x, (const float*)nullptr, (const float*)nullptr, inv, sat, (unsigned*)nullptr)
-#define DIM_CONV6_V(PFV, MD)                              \
-  {                                                       \
-    if (cin == 64 && pool) DIM_CONV6(64, 1, PFV, MD);     \
-    else if (cin == 64) DIM_CONV6(64, 0, PFV, MD);        \
-    else if (pool) DIM_CONV6(128, 1, PFV, MD);            \
-    else DIM_CONV6(128, 0, PFV, MD);                      \
+#define DIM_CONV6(CI, P, PFV, MD, ...) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_x6_kernel<CI, P, PFV, false, MD, false, false, ##__VA_ARGS__>), grid, dim3(256), 0, s, in, wx, bias, out, H, W, cout, relu, tiles_x, (const float*)nullptr, (const float*)nullptr, inv, sat, (unsigned*)nullptr)
+#define DIM_CONV6_V(PFV, MD, ...)                                      \
+  {                                                                    \
+    if (cin == 64 && pool) DIM_CONV6(64, 1, PFV, MD, ##__VA_ARGS__);   \
+    else if (cin == 64) DIM_CONV6(64, 0, PFV, MD, ##__VA_ARGS__);      \
+    else if (pool) DIM_CONV6(128, 1, PFV, MD, ##__VA_ARGS__);          \
+    else DIM_CONV6(128, 0, PFV, MD, ##__VA_ARGS__);                    \
   }
-  if (wt.mode == 2) {
+  if (bn) {  // the BatchNorm epilogue exists with one prefetch variant
+    if (wt.mode == 2) DIM_CONV6_V(1, 2, 2, false, true)
+    else DIM_CONV6_V(1, 1, 2, false, true)
+  } else if (wt.mode == 2) {
     DIM_CONV6_V(1, 2)
   } else {
     switch (dim_conv_x6_variant() & 3) {
@@ -457,19 +490,26 @@ int launch_conv3x3_x6(const float* in, const SplitWeights& wt, const float* bias
 // conv1a (1 -> 64) fused into the 64 -> cout convolution that consumes it (SuperPoint conv1a + conv1b, SPN:161-162).
 int launch_conv3x3_x6_fused1a(const float* image, const float* w1a_tap_cout, const float* b1a, const SplitWeights& wt, const float* bias,
                               float* out, int batch, int H, int W, int cout, int pool, int relu, int planes_out, hipStream_t s,
-                              unsigned* sat, unsigned* sat_image) {
+                              unsigned* sat, unsigned* sat_image, int bn) {
   DIM_REQUIRE(cout % 64 == 0, "conv3x3_x6 fused conv1a: cout=%d must be a multiple of 64", cout);
   DIM_REQUIRE(wt.dev && (wt.mode == 1 || wt.mode == 2), "conv3x3_x6: weights not prepared (mode %d)", wt.mode);
   if (batch <= 0 || H <= 0 || W <= 0) return 0;
   const int var = dim_conv_x6_variant();
-  const bool big = wt.mode == 2 && planes_out && pool && (var & 16);   // the production shape has the 16-row tile variant
+  // the production shape has the 16-row tile variant.  bn: fp16x3 ALWAYS runs 16-row tiles, pre-split output or not — conv1a's s | t are 8 more
+  // live VGPRs in the staging loop, which the 8-row fp16x3 kernels (at the 168-VGPR limit of 3 workgroups per CU) could only take by spilling
+  const bool big = wt.mode == 2 && pool && (bn || (planes_out && (var & 16)));
   const int mr = big ? 4 : 2;
   const int tiles_x = cdiv(W, TW), tiles_y = cdiv(H, tile_rows(mr));
   dim3 grid(tiles_x * tiles_y, cout / 64, batch);
   DIM_REQUIRE(!planes_out || wt.mode == 2, "conv3x3_x6: pre-split output planes exist for the fp16x3 mode only");
-  DIM_REQUIRE(!planes_out || relu, "conv3x3_x6: a pre-split output implies ReLU (its clamp starts at 0)");
+  DIM_REQUIRE(!planes_out || relu || bn, "conv3x3_x6: a pre-split output implies ReLU (its clamp starts at 0)");
+  DIM_REQUIRE(!bn || pool, "conv3x3_x6 fused conv1a: the BatchNorm epilogue exists for the pooled form only");
 #define DIM_CONV6F(P, MD, PO, ...) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_x6_kernel<64, P, 1, true, MD, false, PO, ##__VA_ARGS__>), grid, dim3(256), 0, s, image, wt.dev, bias, out, H, W, cout, relu, tiles_x, w1a_tap_cout, b1a, wt.inv_ch(), sat, sat_image)
-  if (big) DIM_CONV6F(1, 2, true, 4, true);
+  if (bn) {
+    if (big && planes_out) DIM_CONV6F(1, 2, true, 4, true, true);
+    else if (big) DIM_CONV6F(1, 2, false, 4, true, true);
+    else DIM_CONV6F(1, 1, false, 2, false, true);
+  } else if (big) DIM_CONV6F(1, 2, true, 4, true);
   else if (wt.mode == 2 && planes_out) { if (pool) DIM_CONV6F(1, 2, true); else DIM_CONV6F(0, 2, true); }
   else if (wt.mode == 2) { if (pool) DIM_CONV6F(1, 2, false); else DIM_CONV6F(0, 2, false); }
   else { if (pool) DIM_CONV6F(1, 1, false); else DIM_CONV6F(0, 1, false); }
@@ -480,10 +520,11 @@ int launch_conv3x3_x6_fused1a(const float* image, const float* w1a_tap_cout, con
 
 // fp16x3 convolution whose input and / or output are pre-split fp16 planes (see PIN / POUT above)
 int launch_conv3x3_x6_planes(const float* in, const SplitWeights& wt, const float* bias, float* out, int batch, int H, int W, int cin,
-                             int cout, int pool, int relu, int planes_in, int planes_out, hipStream_t s, unsigned* sat) {
+                             int cout, int pool, int relu, int planes_in, int planes_out, hipStream_t s, unsigned* sat, int bn) {
   DIM_REQUIRE(cout % 64 == 0 && (cin == 64 || cin == 128), "conv3x3_x6 planes: cin=%d cout=%d", cin, cout);
   DIM_REQUIRE(wt.dev && wt.mode == 2, "conv3x3_x6 planes: fp16x3 weights required (mode %d)", wt.mode);
-  DIM_REQUIRE(!planes_out || relu, "conv3x3_x6 planes: a pre-split output implies ReLU (its clamp starts at 0)");
+  DIM_REQUIRE(!planes_out || relu || bn, "conv3x3_x6 planes: a pre-split output implies ReLU (its clamp starts at 0)");
+  DIM_REQUIRE(!bn || (planes_in && planes_out), "conv3x3_x6 planes: the BatchNorm epilogue exists for pre-split input AND output only");
   if (batch <= 0 || H <= 0 || W <= 0) return 0;
   const int var = dim_conv_x6_variant();
   // 16-row tiles unless they leave most of the chip idle: ONE image per call (the plugin hooks) gives the 128 x 128 maps of conv4a .. convDa 8 x 4 tiles
@@ -495,7 +536,9 @@ int launch_conv3x3_x6_planes(const float* in, const SplitWeights& wt, const floa
 #define DIM_CONV6P(CI, P, PI, PO, ...) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_x6_kernel<CI, P, 1, false, 2, PI, PO, ##__VA_ARGS__>), grid, dim3(256), 0, s, in, wt.dev, bias, out, H, W, cout, relu, tiles_x, (const float*)nullptr, (const float*)nullptr, wt.inv_ch(), sat, (unsigned*)nullptr)
 #define DIM_CONV6P_IO(CI, P)                                   \
   {                                                            \
-    if (big && planes_out) DIM_CONV6P(CI, P, true, true, 4, true);   \
+    if (bn && big) DIM_CONV6P(CI, P, true, true, 4, true, true);     \
+    else if (bn) DIM_CONV6P(CI, P, true, true, 2, false, true);      \
+    else if (big && planes_out) DIM_CONV6P(CI, P, true, true, 4, true);   \
     else if (big) DIM_CONV6P(CI, P, true, false, 4, true);           \
     else if (planes_in && planes_out) DIM_CONV6P(CI, P, true, true); \
     else if (planes_in) DIM_CONV6P(CI, P, true, false);        \

@@ -93,15 +93,18 @@ int launch_conv3x3(const float* in, const float* w, const float* bias, float* ou
 size_t conv_split_weight_elems(int cin, int cout, int mode);
 void prepare_conv_weights_split(const float* w_oihw, int cin, int cout, int mode, unsigned short* out, SplitWeights* sw);
 // `sat` (all x6 conv launchers): fp16x3 range-guard counter for the outputs (dim_common.h), nullptr = unchecked
+// `bn` (all x6 conv launchers): the epilogue is y = s * relu(conv + b) + t (BatchNorm in eval mode behind the ReLU, ahead of the pool) with
+// bias = [b | s | t], cout floats each (fused conv1a: b1a = [b | s | t], 64 each); `relu` is not consulted.  Exists for the shapes the open
+// SuperPoint takes: pooled fused conv1a, pre-split input AND output in the planes launcher, any launch_conv3x3_x6 shape.
 int launch_conv3x3_x6(const float* in, const SplitWeights& wt, const float* bias, float* out, int batch, int H, int W, int cin,
-                      int cout, int pool, int relu, hipStream_t s, unsigned* sat = nullptr);
+                      int cout, int pool, int relu, hipStream_t s, unsigned* sat = nullptr, int bn = 0);
 // conv1a (image -> 64 channels, weights [9][64]) computed on the fly inside the following 64 -> cout conv
 int launch_conv3x3_x6_fused1a(const float* image, const float* w1a_tap_cout, const float* b1a, const SplitWeights& wt, const float* bias,
                               float* out, int batch, int H, int W, int cout, int pool, int relu, int planes_out, hipStream_t s,
-                              unsigned* sat = nullptr, unsigned* sat_image = nullptr);
+                              unsigned* sat = nullptr, unsigned* sat_image = nullptr, int bn = 0);
 // fp16x3 only: input and / or output pre-split in the bytes of the fp32 NHWC tensor: per pixel and 16-channel group, 16 h then 16 l fp16 pieces (conv_x6.hip)
 int launch_conv3x3_x6_planes(const float* in, const SplitWeights& wt, const float* bias, float* out, int batch, int H, int W, int cin,
-                             int cout, int pool, int relu, int planes_in, int planes_out, hipStream_t s, unsigned* sat = nullptr);
+                             int cout, int pool, int relu, int planes_in, int planes_out, hipStream_t s, unsigned* sat = nullptr, int bn = 0);
 // Winograd F(2,3)-along-x variant of the fused conv1a + 3x3 convolution (conv_wg.hip): fp16x3 only, 2/3 of the MFMAs
 size_t conv_wino_weight_elems(int cin, int cout);
 void prepare_conv_weights_wino(const float* w_oihw, int cin, int cout, unsigned short* out, SplitWeights* sw);

@@ -34,24 +34,18 @@ struct dim_sp {
   bool head_fused;    // the last extract ran convPb + softmax + depth-to-space as one kernel: h->logits is stale
   float* b1_dbg;      // fp32 copy of conv1b's pooled output (dim_sp_debug_conv1b)
   float* x_dbg;       // fp32 copy of it, built on request by dim_sp_debug_buffers
+  bool bn;            // dim_spo_create: the encoder layers' bias buffers are [b | s | t] and their convolutions run the BatchNorm epilogue
 };
 
 namespace {
 const int kCin[12] = {1, 64, 64, 64, 64, 128, 128, 128, 128, 256, 128, 256};
 const int kCout[12] = {64, 64, 64, 64, 128, 128, 128, 128, 256, 65, 256, 256};
 const int kK[12] = {3, 3, 3, 3, 3, 3, 3, 3, 3, 1, 3, 1};
-}  // namespace
 
-extern "C" {
-
-void dim_sp_destroy(dim_sp* h) {
-  if (!h) return;
-  dim_handle_release(&h->base);
-  delete h;
-}
-
-int dim_sp_create(const dim_sp_weights* w, const dim_sp_config* cfg, int max_batch, int max_h, int max_w, int capacity,
-                  dim_sp** out) {
+// Both kinds of handle.  bn_st == nullptr: SuperPoint (dim_sp_create).  Otherwise bn_st[l] = s[cout] | t[cout] of encoder layer l (0 .. 7), stored
+// behind that layer's bias for the BatchNorm epilogue of conv_x6.hip, and w holds the 1x1 heads with their BatchNorms already folded in.
+int sp_create(const dim_sp_weights* w, const std::vector<float>* bn_st, const dim_sp_config* cfg, int max_batch, int max_h, int max_w, int capacity,
+              dim_sp** out) {
   DIM_REQUIRE(w && cfg && out, "dim_sp_create: null argument");
   DIM_REQUIRE(max_batch > 0 && max_h >= 8 && max_w >= 8, "dim_sp_create: bad sizes");
   DIM_REQUIRE(cfg->max_keypoints != 0 && cfg->max_keypoints >= -1, "\"max_keypoints\" must be positive or \"-1\"");  // SPN:152-154
@@ -65,6 +59,7 @@ int dim_sp_create(const dim_sp_weights* w, const dim_sp_config* cfg, int max_bat
   h->max_batch = max_batch; h->max_h = max_h; h->max_w = max_w; h->capacity = capacity;
   h->last_h = h->last_w = h->last_batch = 0;
   h->b1_dbg = nullptr; h->x_dbg = nullptr; h->head_fused = false;
+  h->bn = bn_st != nullptr;
   // ---- weights: OIHW (SPN:128-143) -> [tap][cin][cout] / [cin][cout_padded4] ----
   for (int l = 0; l < 12; ++l) {
     const int ci = kCin[l], co = kCout[l], k = kK[l];
@@ -100,12 +95,14 @@ int dim_sp_create(const dim_sp_weights* w, const dim_sp_config* cfg, int max_bat
     DIM_TRY(dim_upload_f32(hb, &h->wk[l], host));
     std::vector<float> bv(co_pad, 0.0f);
     memcpy(bv.data(), w->conv_b[l], co * sizeof(float));
+    if (bn_st && l < 8) bv.insert(bv.end(), bn_st[l].begin(), bn_st[l].end());   // (co_pad == co for these layers)
     DIM_TRY(dim_upload_f32(hb, &h->bias[l], bv));
   }
   h->conv1a_bound = 0.0f;
   for (int o = 0; o < 64; ++o) {
     float sum = fabsf(w->conv_b[0][o]);
     for (int t = 0; t < 9; ++t) sum += fabsf(w->conv_w[0][o * 9 + t]);
+    if (bn_st) sum = fabsf(bn_st[0][o]) * sum + fabsf(bn_st[0][64 + o]);  // conv1a's BatchNorm follows its ReLU: |s| bound + |t|
     h->conv1a_bound = fmaxf(h->conv1a_bound, sum);
   }
   // ---- activations ----
@@ -135,6 +132,72 @@ int dim_sp_create(const dim_sp_weights* w, const dim_sp_config* cfg, int max_bat
   *out = guard.release();
   return 0;
 }
+}  // namespace
+
+extern "C" {
+
+void dim_sp_destroy(dim_sp* h) {
+  if (!h) return;
+  dim_handle_release(&h->base);
+  delete h;
+}
+
+int dim_sp_create(const dim_sp_weights* w, const dim_sp_config* cfg, int max_batch, int max_h, int max_w, int capacity,
+                  dim_sp** out) {
+  return sp_create(w, nullptr, cfg, max_batch, max_h, max_w, capacity, out);
+}
+
+int dim_spo_create(const dim_spo_weights* w, const dim_sp_config* cfg, int max_batch, int max_h, int max_w, int capacity, dim_sp** out) {
+  DIM_REQUIRE(w && cfg && out, "dim_spo_create: null argument");
+  DIM_REQUIRE(isfinite(w->bn_eps), "dim_spo_create: bn_eps is not finite");
+  // s = gamma / sqrt(var + eps), t = beta - mean s, in double
+  std::vector<double> s[12], t[12];
+  for (int l = 0; l < 12; ++l) {
+    const int ci = kCin[l], co = kCout[l], k = kK[l];
+    DIM_REQUIRE(w->conv_w[l] && w->conv_b[l] && w->bn_gamma[l] && w->bn_beta[l] && w->bn_mean[l] && w->bn_var[l], "dim_spo_create: null tensor in layer %d", l);
+    if (!dim_all_finite(w->conv_w[l], (size_t)k * k * ci * co) || !dim_all_finite(w->conv_b[l], (size_t)co) || !dim_all_finite(w->bn_gamma[l], (size_t)co) ||
+        !dim_all_finite(w->bn_beta[l], (size_t)co) || !dim_all_finite(w->bn_mean[l], (size_t)co) || !dim_all_finite(w->bn_var[l], (size_t)co)) {
+      dim_set_error("dim_spo_create: non-finite value in the weights of layer %d", l);
+      return -1;
+    }
+    s[l].resize(co); t[l].resize(co);
+    for (int o = 0; o < co; ++o) {
+      const double v = (double)w->bn_var[l][o] + w->bn_eps;
+      DIM_REQUIRE(v > 0.0, "dim_spo_create: running_var + eps = %g <= 0 in layer %d, channel %d", v, l, o);
+      s[l][o] = (double)w->bn_gamma[l][o] / sqrt(v);
+      t[l][o] = (double)w->bn_beta[l][o] - (double)w->bn_mean[l][o] * s[l][o];
+      DIM_REQUIRE(isfinite((float)s[l][o]) && isfinite((float)t[l][o]), "dim_spo_create: BatchNorm of layer %d, channel %d is not finite in fp32", l, o);
+    }
+  }
+  std::vector<float> st[8];
+  for (int l = 0; l < 8; ++l) {
+    const int co = kCout[l];
+    st[l].resize(2 * (size_t)co);
+    for (int o = 0; o < co; ++o) { st[l][o] = (float)s[l][o]; st[l][co + o] = (float)t[l][o]; }
+  }
+  // The heads: a = relu(conv3x3(x) + b) keeps the plain epilogue; z = s_a a + t_a, u = W z + b, out = s_b u + t_b is the 1x1 convolution
+  // W'[o][i] = s_b[o] W[o][i] s_a[i], b'[o] = s_b[o] (b[o] + sum_i W[o][i] t_a[i]) + t_b[o] — a 1x1 convolution has no padding: exact.
+  dim_sp_weights f;
+  std::vector<float> fw[2], fb[2];
+  for (int l = 0; l < 12; ++l) { f.conv_w[l] = w->conv_w[l]; f.conv_b[l] = w->conv_b[l]; }
+  for (int hd = 0; hd < 2; ++hd) {
+    const int la = 8 + 2 * hd, lb = la + 1, ci = kCin[lb], co = kCout[lb];
+    fw[hd].resize((size_t)co * ci); fb[hd].resize(co);
+    for (int o = 0; o < co; ++o) {
+      double acc = (double)w->conv_b[lb][o];
+      for (int i = 0; i < ci; ++i) {
+        const double wv = (double)w->conv_w[lb][(size_t)o * ci + i];
+        acc += wv * t[la][i];
+        fw[hd][(size_t)o * ci + i] = (float)(s[lb][o] * wv * s[la][i]);
+      }
+      fb[hd][o] = (float)(s[lb][o] * acc + t[lb][o]);
+    }
+    f.conv_w[lb] = fw[hd].data(); f.conv_b[lb] = fb[hd].data();
+  }
+  dim_sp_config c = *cfg;
+  c.fix_sampling = 1;   // the open network's one sampler (superpoint_pytorch.py sample_descriptors)
+  return sp_create(&f, st, &c, max_batch, max_h, max_w, capacity, out);
+}
 
 int dim_sp_extract(dim_sp* h, const float* images_dev, int batch, int H, int W, float* kpts_xy_dev, float* scores_dev,
                    float* desc_dev, int32_t* n_kpts_dev, void* stream) {
@@ -150,13 +213,16 @@ int dim_sp_extract(dim_sp* h, const float* images_dev, int batch, int H, int W, 
 #define SP_SITE(id, x) do { dim_prof_begin(id, s); SP_RUN(x); dim_prof_end(id, s); } while (0)
   const int pmode = dim_precision_mode();  // 2 (default) fp16x3 / 1 bf16x6: fp32-accurate products on the 16-bit matrix cores; 0: fp32 MFMA
   const bool x6 = pmode != 0;
+  const int bn = h->bn ? 1 : 0;
+  DIM_REQUIRE(!bn || (x6 && dim_fuse_conv1a() && !(dim_conv_winograd() & 1)),
+              "dim_sp_extract: an open-SuperPoint handle (dim_spo_create) runs in fp16x3 / bf16x6 with the fused conv1a only (dim_tune_set keys 1, 3, 15)");
   // fp16x3 range guard (dim_common.h): producers of values that a later split consumes report max|x| > 4094
   unsigned* sat_enc = pmode == 2 ? dim_sat_counter(DIM_SAT_SP_ENCODER) : nullptr;
   unsigned* sat_head = pmode == 2 ? dim_sat_counter(DIM_SAT_SP_HEADS) : nullptr;
   unsigned* sat_img = pmode == 2 ? dim_sat_counter(DIM_SAT_SP_IMAGE) : nullptr;
   if (pmode == 2 && !(h->conv1a_bound <= DIM_F16_ACT_LIMIT)) dim_sat_host_bump(DIM_SAT_SP_IMAGE);  // conv1a's outputs may leave the range
   auto conv = [&](int l, const float* in, float* out, int Hh, int Ww, int ci, int co, int pool) -> int {
-    return x6 ? launch_conv3x3_x6(in, h->wsp[pmode][l], h->bias[l], out, batch, Hh, Ww, ci, co, pool, 1, s, l >= 8 ? sat_head : sat_enc)
+    return x6 ? launch_conv3x3_x6(in, h->wsp[pmode][l], h->bias[l], out, batch, Hh, Ww, ci, co, pool, 1, s, l >= 8 ? sat_head : sat_enc, l < 8 ? bn : 0)
               : launch_conv3x3(in, h->wk[l], h->bias[l], out, batch, Hh, Ww, ci, co, pool, 1, s);
   };
   // encoder (SPN:161-171)
@@ -164,7 +230,7 @@ int dim_sp_extract(dim_sp* h, const float* images_dev, int batch, int H, int W, 
   // each value is split once by its producer instead of ~1.3 x (cout / 64) times by its consumers
   const bool planes = pmode == 2 && dim_fuse_conv1a() && dim_presplit_activations();
   auto convp = [&](int l, const float* in, float* out, int Hh, int Ww, int ci, int co, int pool, int pin, int pout) -> int {
-    return launch_conv3x3_x6_planes(in, h->wsp[2][l], h->bias[l], out, batch, Hh, Ww, ci, co, pool, 1, pin, pout, s, l >= 8 ? sat_head : sat_enc);
+    return launch_conv3x3_x6_planes(in, h->wsp[2][l], h->bias[l], out, batch, Hh, Ww, ci, co, pool, 1, pin, pout, s, l >= 8 ? sat_head : sat_enc, l < 8 ? bn : 0);
   };
 #ifdef DIM_RESEARCH
   if (pmode == 2 && dim_fuse_conv1a() && (dim_conv_winograd() & 1)) {  // Winograd F(2,3) along x: 2/3 of the MFMAs (conv_wg.hip)
@@ -174,7 +240,7 @@ int dim_sp_extract(dim_sp* h, const float* images_dev, int batch, int H, int W, 
   } else
 #endif
   if (x6 && dim_fuse_conv1a()) {  // conv1a evaluated inside conv1b's halo staging: its 64-channel full-resolution map never exists
-    SP_SITE(DIM_PROF_SP_CONV1B, launch_conv3x3_x6_fused1a(images_dev, h->wk[0], h->bias[0], h->wsp[pmode][1], h->bias[1], h->b1, batch, H, W, 64, 1, 1, planes ? 1 : 0, s, sat_enc, sat_img));
+    SP_SITE(DIM_PROF_SP_CONV1B, launch_conv3x3_x6_fused1a(images_dev, h->wk[0], h->bias[0], h->wsp[pmode][1], h->bias[1], h->b1, batch, H, W, 64, 1, 1, planes ? 1 : 0, s, sat_enc, sat_img, bn));
   } else {
     if (!h->a1) SP_RUN(dim_dev_alloc(&h->base, &h->a1, (size_t)h->max_batch * h->max_h * h->max_w * 64));
     SP_SITE(DIM_PROF_SP_CONV1A, launch_conv1a(images_dev, h->wk[0], h->bias[0], h->a1, batch, H, W, s));
@@ -275,7 +341,7 @@ int dim_sp_debug_conv1b(dim_sp* h, int batch, int H, int W, const float** out_f3
   DimTuneScope tune_scope(&h->base);
   const int H2 = H / 2, W2 = W / 2;
   if (!h->b1_dbg && dim_dev_alloc(&h->base, &h->b1_dbg, (size_t)h->max_batch * (h->max_h / 2) * (h->max_w / 2) * 64) != 0) return -1;
-  const bool planes = dim_precision_mode() == 2 && dim_fuse_conv1a() && dim_presplit_activations();
+  const bool planes = h->x_is_planes;   // how the last extract stored b1 .. x (a guarded call may have re-run in another arithmetic than the current one)
   if (planes) {
     if (launch_planes_to_f32(h->b1, batch, H2 * W2, 64, h->b1_dbg, nullptr) != 0) return -1;
   } else {

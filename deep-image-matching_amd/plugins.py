@@ -9,7 +9,8 @@ error behaviour, with the network replaced by the gfx950 library.  When the real
 ``MatcherBase`` (so ``extractor_loader`` / ``matcher_loader`` discover them, extractor_base.py:29-52,
 matcher_base.py:36-60); otherwise a minimal stand-in base with the same constructor contract
 (extractor_base.py:119-160) is used so the hooks can be driven and tested on their own.
-``KorniaMatcher`` mirrors matchers/kornia_matcher.py:9-53 (nearest-neighbour descriptor matching, no weights).
+``KorniaMatcher`` mirrors matchers/kornia_matcher.py:9-53 (nearest-neighbour descriptor matching, no weights);
+``SuperPointOpenExtractor`` mirrors extractors/superpoint_open.py:72-164 (the openly licensed SuperPoint).
 See INTEGRATION.md for the module files a maintainer adds to the reference tree.
 """
 from __future__ import annotations
@@ -28,7 +29,7 @@ from .alike_hip import AlikeHIP
 from .aliked_hip import AlikedHIP
 from .lightglue_hip import LightGlueHIP
 from .nn_hip import NearestNeighborHIP, check_mode as _check_nn_mode
-from .superpoint_hip import SuperPointHIP
+from .superpoint_hip import SuperPointHIP, SuperPointOpenHIP
 from .tile_matching import BatchedTileMatchingMixin
 from .tiling import BatchedTilingMixin
 
@@ -391,6 +392,76 @@ class AlikeExtractor(_ExtractorBase):
     def _frame2tensor(self, image: np.ndarray, device: str = "cuda"):
         """AKX:46-54: the reference's hook is empty (ALike.forward converts the array itself)."""
         return None
+
+
+class SuperPointOpenExtractor(_ExtractorBase):
+    """extractors/superpoint_open.py:72 — the openly licensed SuperPoint (thirdparty/SuperPoint_open) on the gfx950 library: every block
+    conv -> ReLU -> BatchNorm(eval) with the BatchNorm in the convolution's epilogue.  DEVIATION, stated in INTEGRATION.md: with the class
+    default ``max_keypoints = -1`` the reference's network raises inside torch.topk; here -1 keeps every keypoint (row-major order)."""
+
+    _default_conf = {  # extractors/superpoint_open.py:94-101 (name and fix_sampling as the reference has them: its network knows one sampler)
+        "name": "superpoint",
+        "nms_radius": 4,
+        "keypoint_threshold": 0.005,
+        "max_keypoints": -1,
+        "remove_borders": 4,
+        "fix_sampling": False,
+    }
+    required_inputs = ["image"]
+    grayscale = True
+    descriptor_size = 256
+    detection_noise = 2.0
+
+    def __init__(self, config):
+        super().__init__(config)
+        self._lib = capi.load()
+        self._device = _resolve_device(self._device, "SuperPointOpenExtractor")
+        cfg = self.config.get("extractor")
+        self._arith = _apply_arithmetic(cfg, self._lib)
+        self._on_sat = _saturation_policy(cfg)
+        path = cfg.get("weights_path") or os.environ.get("DIM_SUPERPOINT_OPEN_WEIGHTS")
+        if path is None and cfg.get("allow_synthetic_weights"):
+            logger.warning("SuperPoint (open): running on seeded SYNTHETIC weights (allow_synthetic_weights) - test / benchmark use only")
+        self._sd = _weights.load_superpoint_open_state_dict(path, allow_synthetic=bool(cfg.get("allow_synthetic_weights", False)))
+        self._net_cfg = {k: cfg[k] for k in ("nms_radius", "keypoint_threshold", "max_keypoints", "remove_borders")}
+        self._net: Optional[SuperPointOpenHIP] = None
+        self._net_hw = (0, 0)
+        self._min_capacity = 0
+
+    _capacity = SuperPointExtractor._capacity   # the slot size and the keep-all regrow are SuperPoint's
+    _regrow = SuperPointExtractor._regrow
+
+    def _ensure(self, H: int, W: int):
+        cap = self._capacity(H, W)
+        if self._net is None or H > self._net_hw[0] or W > self._net_hw[1] or cap > self._net.capacity:
+            hw = (max(H, self._net_hw[0]), max(W, self._net_hw[1]))
+            self._net = SuperPointOpenHIP(self._sd, self._net_cfg, max_batch=1, max_hw=hw, capacity=cap,
+                                          device=self._device, lib=self._lib, on_saturation=self._on_sat, arithmetic=self._arith)
+            self._net_hw = hw
+
+    @torch.no_grad()
+    def _extract(self, image: np.ndarray) -> dict:
+        """image: float32 HxW, values 0..255.  Zero-padded at the bottom and the right to multiples of 8 as the reference's hook does
+        (extractors/superpoint_open.py:131-135; borders are removed relative to the PADDED frame and keypoints inside the padding are kept, as
+        there).  Returns numpy keypoints (N,2) float32 (x,y), scores (N,), descriptors (256,N)."""
+        a = _frame2array(image)
+        if a.shape[1] != 1:
+            raise ValueError("SuperPoint expects a single-channel image")
+        H, W = int(a.shape[-2]), int(a.shape[-1])
+        Hp, Wp = -(-H // 8) * 8, -(-W // 8) * 8
+        if (Hp, Wp) != (H, W):
+            a = np.pad(a, [(0, 0), (0, 0), (0, Hp - H), (0, Wp - W)])
+        self._ensure(Hp, Wp)
+        img = _to_device(self, a, self._device).reshape(1, Hp, Wp)
+        out = self._net.extract_batch_guarded(img)
+        if self._regrow(self._net, 1):
+            self._ensure(Hp, Wp)
+            out = self._net.extract_batch_guarded(img)
+        return _features_to_numpy(self, out)
+
+    def _frame2tensor(self, image: np.ndarray, device: str = "cuda"):
+        """extractors/superpoint_open.py:152-164 (through page-locked staging on a GPU)."""
+        return _to_device(self, _frame2array(image), device, sync=True)
 
 
 def featuresDict2Lightglue(feats: dict) -> dict:

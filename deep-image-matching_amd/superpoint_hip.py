@@ -13,7 +13,7 @@ from typing import Dict, Optional
 import torch
 
 from . import capi
-from .weights import SP_LAYERS
+from .weights import SP_LAYERS, SPO_BLOCKS, SPO_BN_EPS, validate_superpoint_open_state_dict
 
 
 class _SpWeights(ctypes.Structure):
@@ -122,3 +122,42 @@ class SuperPointHIP(capi.ResidentHandle):
         p, h2, w2 = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
         capi.check(self.lib, self.lib.dim_sp_debug_conv1b(self._h, int(batch), int(H), int(W), ctypes.byref(p), ctypes.byref(h2), ctypes.byref(w2)))
         return capi.copy_from_device(self.lib, p.value, (batch, h2.value, w2.value, 64), self.device)
+
+
+class _SpoWeights(ctypes.Structure):
+    """include/dim_hip.h: dim_spo_weights."""
+    _fields_ = [(n, ctypes.c_void_p * 12) for n in ("conv_w", "conv_b", "bn_gamma", "bn_beta", "bn_mean", "bn_var")] + [("bn_eps", ctypes.c_double)]
+
+
+class SuperPointOpenHIP(SuperPointHIP):
+    """Resident open SuperPoint (thirdparty/SuperPoint_open/superpoint_pytorch.py) on one GPU: dim_spo_create returns an ordinary dim_sp handle, so
+    extract_batch, the guard, the debug taps and candidate_counts are the base class's.  ``state_dict`` in the checkpoint's key layout
+    (weights.load_superpoint_open_state_dict); cfg keys as SuperPointHIP — fix_sampling is always on (the network has the one sampler), and
+    max_keypoints = -1 keeps every keypoint (the reference network would raise inside torch.topk)."""
+
+    default_config = {**SuperPointHIP.default_config, "fix_sampling": True}
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: Optional[dict] = None, max_batch: int = 1,
+                 max_hw=(1024, 1024), capacity: Optional[int] = None, device="cuda", lib=None, on_saturation: str = "fallback", arithmetic=None):
+        validate_superpoint_open_state_dict(state_dict)   # KeyError / ValueError naming the tensor, before any native call
+        self.cfg = {**self.default_config, **(cfg or {}), "fix_sampling": True}
+        mk = self.cfg["max_keypoints"]
+        if mk == 0 or mk < -1:
+            raise ValueError('"max_keypoints" must be positive or "-1"')
+        if arithmetic == "fp32":
+            raise ValueError("SuperPointOpenHIP: the BatchNorm epilogue exists in the fp16x3 / bf16x6 arithmetic only")
+        self._open(device, lib, on_saturation, arithmetic)
+        self.max_batch, self.max_hw = int(max_batch), (int(max_hw[0]), int(max_hw[1]))
+        self.capacity = int(capacity if capacity is not None else (mk if mk > 0 else 8192))
+        w = _SpoWeights()
+        for i, blk in enumerate(SPO_BLOCKS):
+            w.conv_w[i] = self._host(state_dict[blk + ".conv.weight"])
+            w.conv_b[i] = self._host(state_dict[blk + ".conv.bias"])
+            w.bn_gamma[i] = self._host(state_dict[blk + ".bn.weight"])
+            w.bn_beta[i] = self._host(state_dict[blk + ".bn.bias"])
+            w.bn_mean[i] = self._host(state_dict[blk + ".bn.running_mean"])
+            w.bn_var[i] = self._host(state_dict[blk + ".bn.running_var"])
+        w.bn_eps = SPO_BN_EPS
+        c = _SpConfig(int(self.cfg["nms_radius"]), float(self.cfg["keypoint_threshold"]), int(mk), int(self.cfg["remove_borders"]), 1)
+        self.lib.dim_spo_create.restype = ctypes.c_int
+        self._create(self.lib.dim_spo_create, ctypes.byref(w), ctypes.byref(c), self.max_batch, self.max_hw[0], self.max_hw[1], self.capacity)

@@ -305,3 +305,80 @@ def load_alike_state_dict(path: str | None = None, model: str = "alike-s", seed:
     sd = {k: (v.float().contiguous() if v.is_floating_point() else v) for k, v in sd.items()}
     validate_alike_state_dict(sd, model)
     return sd
+
+
+# ---- the open SuperPoint (thirdparty/SuperPoint_open/superpoint_pytorch.py; checkpoint superpoint_v6_from_tf.pth) ----------------------------
+# block prefix per layer, in SP_LAYERS order: backbone.{stage}.{0,1} = conv{stage+1}{a,b}, detector.{0,1} = convPa / convPb, descriptor.{0,1} = convDa / convDb
+SPO_BLOCKS = [f"backbone.{i}.{j}" for i in range(4) for j in range(2)] + ["detector.0", "detector.1", "descriptor.0", "descriptor.1"]
+SPO_BN_EPS = 1e-3  # VGGBlock: nn.BatchNorm2d(c_out, eps=0.001)
+
+
+def superpoint_open_state_dict_shapes() -> Dict[str, tuple]:
+    """Every tensor of the open SuperPoint's checkpoint and its shape: per block conv.{weight, bias} and bn.{weight, bias, running_mean, running_var}
+    (+ the optional scalar bn.num_batches_tracked), with the layer geometry of SP_LAYERS."""
+    t: Dict[str, tuple] = {}
+    for blk, (_, co, ci, k) in zip(SPO_BLOCKS, SP_LAYERS):
+        t[f"{blk}.conv.weight"] = (co, ci, k, k)
+        t[f"{blk}.conv.bias"] = (co,)
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            t[f"{blk}.bn.{leaf}"] = (co,)
+        t[f"{blk}.bn.num_batches_tracked"] = ()
+    return t
+
+
+def validate_superpoint_open_state_dict(sd: Dict[str, torch.Tensor]) -> None:
+    """KeyError for a missing / unexpected tensor, ValueError for a wrong shape, a non-finite value or running_var + eps <= 0 — each naming the
+    tensor — before anything native is called."""
+    table = superpoint_open_state_dict_shapes()
+    for k, shape in table.items():
+        if k not in sd:
+            if k.endswith("num_batches_tracked"):
+                continue
+            raise KeyError(f"SuperPoint (open): state dict has no tensor {k!r}")
+        if tuple(sd[k].shape) != tuple(shape):
+            raise ValueError(f"SuperPoint (open): tensor {k!r} has shape {tuple(sd[k].shape)}, expected {tuple(shape)}")
+        if sd[k].is_floating_point() and not bool(torch.isfinite(sd[k]).all()):
+            raise ValueError(f"SuperPoint (open): tensor {k!r} holds a non-finite value")
+        if k.endswith("running_var") and not bool((sd[k].double() + SPO_BN_EPS > 0).all()):
+            raise ValueError(f"SuperPoint (open): tensor {k!r} has an entry with running_var + eps <= 0")
+    for k in sd:
+        if k not in table:
+            raise KeyError(f"SuperPoint (open): unexpected tensor {k!r} in the state dict")
+
+
+def synthetic_superpoint_open_state_dict(seed: int = 4321, negative_gamma: float = 0.3, off_centre: float = 1.0) -> Dict[str, torch.Tensor]:
+    """Seeded synthetic weights in the checkpoint's layout.  He-normal convolutions, small biases; BatchNorm |gamma| in [0.5, 1) with about
+    ``negative_gamma`` of the channels NEGATIVE (they turn the pool behind the BatchNorm into a min-pool of the ReLU output), beta ~ 0.1 N,
+    running_mean in [0.2, 0.6) and running_var in [0.25, 0.75) — around the mean 0.40 and variance 0.34 of the ReLU of a unit normal, so the
+    activations keep their scale from layer to layer and the 65 logits stay O(1): a score map that is neither uniform nor one-hot.
+    ``off_centre`` < 1 multiplies the eight off-centre taps of the 3x3 kernels of stages 3 and 4 and of the two heads (the kernel is rescaled to
+    its He variance): centre-heavy kernels narrow the effective receptive field, which for He-normal kernels spans most of a small test image
+    (the descriptors of two overlapping crops then differ wherever a crop border is within ~40 px)."""
+    g = torch.Generator().manual_seed(seed)
+    sd: Dict[str, torch.Tensor] = {}
+    for blk, (_, co, ci, k) in zip(SPO_BLOCKS, SP_LAYERS):
+        sd[f"{blk}.conv.weight"] = torch.randn(co, ci, k, k, generator=g) * math.sqrt(2.0 / (ci * k * k))
+        if off_centre != 1.0 and k == 3 and blk.startswith(("backbone.2", "backbone.3", "detector", "descriptor")):
+            m = torch.full((3, 3), float(off_centre))
+            m[1, 1] = 1.0
+            sd[f"{blk}.conv.weight"] *= m * math.sqrt(9.0 / float((m * m).sum()))
+        sd[f"{blk}.conv.bias"] = torch.randn(co, generator=g) * 0.01
+        sign = torch.where(torch.rand(co, generator=g) < negative_gamma, -1.0, 1.0)
+        sd[f"{blk}.bn.weight"] = (0.5 + 0.5 * torch.rand(co, generator=g)) * sign
+        sd[f"{blk}.bn.bias"] = 0.1 * torch.randn(co, generator=g)
+        sd[f"{blk}.bn.running_mean"] = 0.2 + 0.4 * torch.rand(co, generator=g)
+        sd[f"{blk}.bn.running_var"] = 0.25 + 0.5 * torch.rand(co, generator=g)
+        sd[f"{blk}.bn.num_batches_tracked"] = torch.tensor(0)
+    return sd
+
+
+def load_superpoint_open_state_dict(path: str | None = None, seed: int = 4321, allow_synthetic: bool = False) -> Dict[str, torch.Tensor]:
+    """thirdparty/SuperPoint_open/weights/superpoint_v6_from_tf.pth (a plain state dict of superpoint_pytorch.SuperPoint), validated against the
+    one table of keys and shapes.  ``path``: a file name or an open binary file."""
+    if path is None:
+        _no_weights("SuperPoint (open; thirdparty/SuperPoint_open/weights/superpoint_v6_from_tf.pth in the reference tree)", "DIM_SUPERPOINT_OPEN_WEIGHTS", allow_synthetic)
+        return synthetic_superpoint_open_state_dict(seed)
+    sd = torch.load(path if hasattr(path, "read") else str(Path(path)), map_location="cpu")
+    sd = {k: (v.float().contiguous() if v.is_floating_point() else v) for k, v in sd.items()}
+    validate_superpoint_open_state_dict(sd)
+    return sd

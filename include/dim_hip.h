@@ -168,6 +168,27 @@ int dim_sp_debug_conv1b(dim_sp* h, int batch, int H, int W, const float** out_f3
  * (before top-k), device int32 [batch] owned by the handle. */
 int dim_sp_candidate_counts(dim_sp* h, const int32_t** ncand_dev);
 
+/* The openly licensed SuperPoint (reference thirdparty/SuperPoint_open/superpoint_pytorch.py, driven by extractors/superpoint_open.py): the
+ * layer shapes of dim_sp_weights, every block conv -> ReLU -> BatchNorm(eval) with the 2x2 max-pool BEHIND the BatchNorm, the two 1x1 heads
+ * conv -> BatchNorm without ReLU.  Per layer (same order as conv_w) the BatchNorm's weight, bias, running_mean and running_var, [cout] fp32 host
+ * pointers, and the one eps of all of them (the reference: 1e-3). */
+typedef struct dim_spo_weights {
+  const float* conv_w[12];
+  const float* conv_b[12];
+  const float* bn_gamma[12];
+  const float* bn_beta[12];
+  const float* bn_mean[12];
+  const float* bn_var[12];
+  double bn_eps;
+} dim_spo_weights;
+
+/* As dim_sp_create; returns an ordinary dim_sp handle (extract, destroy, the debug taps, candidate counts and the tune keys are shared).  s = gamma /
+ * sqrt(var + eps) and t = beta - mean * s are formed in double; non-finite values and var + eps <= 0 are rejected.  The eight encoder layers apply
+ * s * relu(conv + b) + t in the convolution's epilogue (ahead of the pool); the BatchNorms around the two 1x1 heads are folded into the 1x1
+ * weights exactly.  cfg->fix_sampling is ignored (the open network has the one sampler, = 1).  Such a handle runs in the fp16x3 / bf16x6 arithmetic with
+ * the fused conv1a only: dim_sp_extract returns an error under precision mode 0 or dim_tune_set key 3 = 0. */
+int dim_spo_create(const dim_spo_weights* w, const dim_sp_config* cfg, int max_batch, int max_h, int max_w, int capacity, dim_sp** out);
+
 /* ------------------------------------------------------------------------ */
 /* ALIKED (reference ALN = thirdparty/LightGlue/lightglue/aliked.py:561-693, driven by
  * extractors/aliked.py:45-64)                                               */
