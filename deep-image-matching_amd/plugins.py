@@ -10,7 +10,8 @@ error behaviour, with the network replaced by the gfx950 library.  When the real
 matcher_base.py:36-60); otherwise a minimal stand-in base with the same constructor contract
 (extractor_base.py:119-160) is used so the hooks can be driven and tested on their own.
 ``KorniaMatcher`` mirrors matchers/kornia_matcher.py:9-53 (nearest-neighbour descriptor matching, no weights);
-``SuperPointOpenExtractor`` mirrors extractors/superpoint_open.py:72-164 (the openly licensed SuperPoint).
+``SuperPointOpenExtractor`` mirrors extractors/superpoint_open.py:72-164 (the openly licensed SuperPoint);
+``XfeatExtractor`` mirrors extractors/xfeat.py:11-63 (XFeat's sparse detectAndCompute).
 See INTEGRATION.md for the module files a maintainer adds to the reference tree.
 """
 from __future__ import annotations
@@ -32,6 +33,7 @@ from .nn_hip import NearestNeighborHIP, check_mode as _check_nn_mode
 from .superpoint_hip import SuperPointHIP, SuperPointOpenHIP
 from .tile_matching import BatchedTileMatchingMixin
 from .tiling import BatchedTilingMixin
+from .xfeat_hip import XFeatHIP
 
 logger = logging.getLogger("dim")
 
@@ -461,6 +463,61 @@ class SuperPointOpenExtractor(_ExtractorBase):
 
     def _frame2tensor(self, image: np.ndarray, device: str = "cuda"):
         """extractors/superpoint_open.py:152-164 (through page-locked staging on a GPU)."""
+        return _to_device(self, _frame2array(image), device, sync=True)
+
+
+class XfeatExtractor(_ExtractorBase):
+    """extractors/xfeat.py:11 — XFeat (sparse detectAndCompute) on the gfx950 library.  The reference's quirks are kept: ``detect_threshold`` is
+    read from the config and never handed to the network, which always runs its own 0.05; the image reaches the network in 0..255; the
+    descriptors come back as (N,64) ROWS, not transposed like every other extractor's (and ``descriptor_size`` says 128)."""
+
+    _default_conf = {  # extractors/xfeat.py:12-16
+        "name": "xfeat",
+        "max_num_keypoints": 4000,
+        "detect_threshold": 0.05,
+    }
+    required_inputs = []
+    grayscale = False
+    descriptor_size = 128
+
+    def __init__(self, config):
+        super().__init__(config)
+        self._lib = capi.load()
+        self._device = _resolve_device(self._device, "XfeatExtractor")
+        cfg = self.config.get("extractor")
+        self.max_num_keypoints = int(cfg.get("max_num_keypoints", self._default_conf["max_num_keypoints"]))
+        self._net_cfg = {"top_k": self.max_num_keypoints, "detection_threshold": 0.05}   # (not cfg["detect_threshold"]: extractors/xfeat.py:28-30)
+        arith = _apply_arithmetic(cfg, self._lib)
+        if arith is not None:
+            self._net_cfg["arithmetic"] = arith
+        self._net_cfg["on_saturation"] = _saturation_policy(cfg)
+        path = cfg.get("weights_path") or os.environ.get("DIM_XFEAT_WEIGHTS")
+        if path is None and cfg.get("allow_synthetic_weights"):
+            logger.warning("XFeat: running on seeded SYNTHETIC weights (allow_synthetic_weights) - test / benchmark use only")
+        self._sd = _weights.load_xfeat_state_dict(path, allow_synthetic=bool(cfg.get("allow_synthetic_weights", False)))
+        self._net: Optional[XFeatHIP] = None
+        self._net_hw = (0, 0)
+
+    def _ensure(self, H: int, W: int):
+        if self._net is None or H > self._net_hw[0] or W > self._net_hw[1]:
+            hw = (max(H, self._net_hw[0]), max(W, self._net_hw[1]))
+            self._net = XFeatHIP(self._sd, self._net_cfg, max_batch=1, max_hw=hw, device=self._device, lib=self._lib)
+            self._net_hw = hw
+
+    @torch.no_grad()
+    def _extract(self, image: np.ndarray) -> dict:
+        """image: HxWx3 or HxW, 0..255, handed to the network unscaled (extractors/xfeat.py:37).  Returns numpy keypoints (N,2), scores (N,),
+        descriptors (N,64)."""
+        if image.ndim not in (2, 3):
+            raise RuntimeError("For numpy arrays, only (H,W) or (H,W,C) format is supported.")   # XFM:227
+        a = np.ascontiguousarray(image if image.ndim == 3 else image[..., None], dtype=np.float32)
+        self._ensure(a.shape[0], a.shape[1])
+        kp, sc, de, n = self._net.extract_batch_guarded(torch.from_numpy(a)[None].to(self._device))
+        k = int(n[0].item())
+        return {"keypoints": kp[0, :k].cpu().numpy(), "scores": sc[0, :k].cpu().numpy(), "descriptors": de[0, :k, :64].cpu().numpy()}
+
+    def _frame2tensor(self, image: np.ndarray, device: str = "cuda"):
+        """extractors/xfeat.py:44-56."""
         return _to_device(self, _frame2array(image), device, sync=True)
 
 

@@ -382,3 +382,83 @@ def load_superpoint_open_state_dict(path: str | None = None, seed: int = 4321, a
     sd = {k: (v.float().contiguous() if v.is_floating_point() else v) for k, v in sd.items()}
     validate_superpoint_open_state_dict(sd)
     return sd
+
+
+# ---- XFeat (thirdparty/accelerated_features/modules/model.py; checkpoint weights/xfeat.pt) ---------------------------------------------------
+# BasicLayer = conv (no bias) -> BatchNorm2d(affine=False) in eval mode -> ReLU (model.py:12-25): prefix, cout, cin, kernel, stride
+XFEAT_BASIC = [
+    ("block1.0", 4, 1, 3, 1), ("block1.1", 8, 4, 3, 2), ("block1.2", 8, 8, 3, 1), ("block1.3", 24, 8, 3, 2),
+    ("block2.0", 24, 24, 3, 1), ("block2.1", 24, 24, 3, 1),
+    ("block3.0", 64, 24, 3, 2), ("block3.1", 64, 64, 3, 1), ("block3.2", 64, 64, 1, 1),
+    ("block4.0", 64, 64, 3, 2), ("block4.1", 64, 64, 3, 1), ("block4.2", 64, 64, 3, 1),
+    ("block5.0", 128, 64, 3, 2), ("block5.1", 128, 128, 3, 1), ("block5.2", 128, 128, 3, 1), ("block5.3", 64, 128, 1, 1),
+    ("block_fusion.0", 64, 64, 3, 1), ("block_fusion.1", 64, 64, 3, 1),
+    ("heatmap_head.0", 64, 64, 1, 1), ("heatmap_head.1", 64, 64, 1, 1),
+    ("keypoint_head.0", 64, 64, 1, 1), ("keypoint_head.1", 64, 64, 1, 1), ("keypoint_head.2", 64, 64, 1, 1),
+]
+# plain 1x1 convolutions with a bias: prefix, cout, cin
+XFEAT_BIASED = [("skip1.1", 24, 1), ("block_fusion.2", 64, 64), ("heatmap_head.2", 1, 64), ("keypoint_head.3", 65, 64)]
+XFEAT_BN_EPS = 1e-5
+
+
+def _xfeat_layout():
+    t = []
+    for p, co, ci, k, _ in XFEAT_BASIC:
+        t += [(f"{p}.layer.0.weight", (co, ci, k, k)), (f"{p}.layer.1.running_mean", (co,)), (f"{p}.layer.1.running_var", (co,)),
+              (f"{p}.layer.1.num_batches_tracked", ())]
+    for p, co, ci in XFEAT_BIASED:
+        t += [(f"{p}.weight", (co, ci, 1, 1)), (f"{p}.bias", (co,))]
+    return t
+
+
+XFEAT_LAYOUT = _xfeat_layout()   # (key, shape) of every tensor detectAndCompute uses
+
+
+def validate_xfeat_state_dict(sd: Dict[str, torch.Tensor]) -> None:
+    """KeyError for a missing / unexpected tensor, ValueError for a wrong shape, a non-finite value or a negative running_var — each naming the
+    tensor — before anything native is called.  ``fine_matcher.*`` (used by match_xfeat_star only) and ``num_batches_tracked`` are accepted and
+    ignored, present or not."""
+    table = dict(XFEAT_LAYOUT)
+    for k, shape in XFEAT_LAYOUT:
+        if k not in sd:
+            if k.endswith("num_batches_tracked"):
+                continue
+            raise KeyError(f"XFeat: state dict has no tensor {k!r}")
+        if tuple(sd[k].shape) != tuple(shape):
+            raise ValueError(f"XFeat: tensor {k!r} has shape {tuple(sd[k].shape)}, expected {tuple(shape)}")
+        if sd[k].is_floating_point() and not bool(torch.isfinite(sd[k]).all()):
+            raise ValueError(f"XFeat: tensor {k!r} holds a non-finite value")
+        if k.endswith("running_var") and not bool((sd[k] >= 0).all()):
+            raise ValueError(f"XFeat: tensor {k!r} has a negative entry")
+    for k in sd:
+        if k not in table and not k.startswith("fine_matcher."):
+            raise KeyError(f"XFeat: unexpected tensor {k!r} in the state dict")
+
+
+def synthetic_xfeat_state_dict(seed: int = 21) -> Dict[str, torch.Tensor]:
+    """Seeded synthetic XFeat weights in the checkpoint's layout (without fine_matcher.*): He-normal convolutions, biases and running means
+    0.1 N(0, 1), running variances U(0.5, 1.5)."""
+    g = torch.Generator().manual_seed(seed)
+    sd: Dict[str, torch.Tensor] = {}
+    for k, shape in XFEAT_LAYOUT:
+        if k.endswith("num_batches_tracked"):
+            sd[k] = torch.tensor(0)
+        elif k.endswith("running_var"):
+            sd[k] = 0.5 + torch.rand(shape, generator=g)
+        elif len(shape) == 1:
+            sd[k] = 0.1 * torch.randn(shape, generator=g)
+        else:
+            sd[k] = torch.randn(shape, generator=g) * math.sqrt(2.0 / (shape[1] * shape[2] * shape[3]))
+    return sd
+
+
+def load_xfeat_state_dict(path: str | None = None, seed: int = 21, allow_synthetic: bool = False) -> Dict[str, torch.Tensor]:
+    """thirdparty/accelerated_features/weights/xfeat.pt (a plain state dict of XFeatModel), validated against XFEAT_LAYOUT.
+    ``path``: a file name or an open binary file."""
+    if path is None:
+        _no_weights("XFeat (thirdparty/accelerated_features/weights/xfeat.pt in the reference tree)", "DIM_XFEAT_WEIGHTS", allow_synthetic)
+        return synthetic_xfeat_state_dict(seed)
+    sd = torch.load(path if hasattr(path, "read") else str(Path(path)), map_location="cpu")
+    sd = {k: (v.float().contiguous() if v.is_floating_point() else v) for k, v in sd.items()}
+    validate_xfeat_state_dict(sd)
+    return sd

@@ -99,6 +99,7 @@ enum {
   DIM_SAT_OP,             /* operator-level entry points (dim_op_*_x6) */
   DIM_SAT_ALIKED,         /* ALIKED: inputs of the split-precision convolutions / GEMMs (image, BatchNorm+SELU outputs, SDDH samples) */
   DIM_SAT_ALIKE,          /* ALIKE: activations stored by the encoder / aggregation convolutions, rows and outputs of the head products */
+  DIM_SAT_XFEAT,          /* XFeat: the normalised image, block2's input, the pyramid sum and the activations stored by the trunk convolutions */
   DIM_SAT_SITES = 16
 };
 int dim_saturation_read(unsigned* counts_host, unsigned long long* total, int reset, void* stream);
@@ -272,6 +273,44 @@ int dim_alike_extract(dim_alike* h, const float* images_dev, int batch, int H, i
                       int32_t* n_kpts_dev, void* stream);
 /* Parity taps of the last call: score map [batch][H][W], border-cleared NMS map [batch][H][W] (AKD:102-108), padded frame sizes. */
 int dim_alike_debug_buffers(dim_alike* h, const float** score_map, const float** nms_map, int* hp, int* wp);
+
+/* ------------------------------------------------------------------------ */
+/* XFeat, sparse detectAndCompute (reference XFM = thirdparty/accelerated_features/modules/xfeat.py:50-103,
+ * XFN = modules/model.py:123-154, XFI = modules/interpolator.py, driven by extractors/xfeat.py) */
+/* ------------------------------------------------------------------------ */
+
+/* The tensors of XFeatModel's state dict that detectAndCompute uses (conv weights OIHW, host pointers); fine_matcher.* is not part of it.
+ * A BasicLayer is conv (no bias) -> BatchNorm2d(affine=False) in EVAL mode -> ReLU (XFN:12-25): the BatchNorm is folded into the weights and a
+ * bias at create time in fp64 (eps 1e-5).  Order of the 23 BasicLayers: block1.0-3, block2.0-1, block3.0-2, block4.0-2, block5.0-3,
+ * block_fusion.0-1, heatmap_head.0-1, keypoint_head.0-2 (geometry: XFN:43-92). */
+typedef struct dim_xfeat_weights {
+  const float *basic_w[23], *basic_mean[23], *basic_var[23];   /* <layer>.layer.0.weight, <layer>.layer.1.running_mean / running_var */
+  const float *skip_w, *skip_b;       /* skip1.1: (24,1,1,1), (24) */
+  const float *fusion_w, *fusion_b;   /* block_fusion.2: (64,64,1,1), (64) */
+  const float *heat_w, *heat_b;       /* heatmap_head.2: (1,64,1,1), (1) */
+  const float *kp_w, *kp_b;           /* keypoint_head.3: (65,64,1,1), (65) */
+} dim_xfeat_weights;
+
+typedef struct dim_xfeat_config {
+  int top_k;                   /* the top_k highest keys, score-descending (XFM:83-87; always sorted, also below top_k) */
+  float detection_threshold;   /* NMS threshold on the keypoint heat map (XFM:74), in [0, 1); the reference's extractor always runs the network's 0.05 */
+  int desc_stride;             /* floats per descriptor row: >= 64, <= 128, multiple of 4, 0 = 64; columns [64, desc_stride) are written as zeros */
+} dim_xfeat_config;
+
+typedef struct dim_xfeat dim_xfeat;
+/* top_k <= capacity <= 32768; max_batch <= 64; max_h, max_w >= 32. */
+int dim_xfeat_create(const dim_xfeat_weights* w, const dim_xfeat_config* cfg, int max_batch, int max_h, int max_w, int capacity, dim_xfeat** out);
+void dim_xfeat_destroy(dim_xfeat* h);
+/* images_dev: [batch][H][W][channels] fp32, channels 1 or 3, any scale (the network normalises every image, XFN:135-136); 32 <= H, W <= the handle's
+ * maximum.  The frame is resized bilinearly to (H / 32 * 32, W / 32 * 32) (XFM:236-239; the identity for multiples of 32).
+ * kpts (x, y): integer pixels of the resized frame times (W / _W, H / _H) (XFM:96); scores: keypoint heat x reliability (XFM:79); desc:
+ * [batch][capacity][desc_stride], the bicubically sampled, L2-normalised descriptors (XFM:90-93); rows at or past n_kpts are not written.
+ * As in the reference, a maximum in the last row or column of the resized frame and one at pixel (0, 0) never come out. */
+int dim_xfeat_extract(dim_xfeat* h, const float* images_dev, int batch, int H, int W, int channels, float* kpts_xy_dev, float* scores_dev, float* desc_dev,
+                      int32_t* n_kpts_dev, void* stream);
+/* Parity taps of the last call: the normalised image and the keypoint heat map K1h [batch][_H][_W], the reliability map [batch][_H/8][_W/8], the
+ * L2-normalised dense descriptors [batch][_H/8][_W/8][64], and the resized frame's size. */
+int dim_xfeat_debug_buffers(dim_xfeat* h, const float** norm_image, const float** k1h, const float** h1, const float** m1, int* hr, int* wr);
 
 /* ------------------------------------------------------------------------ */
 /* LightGlue (reference LGN:300-610)                                        */
@@ -468,6 +507,15 @@ size_t dim_op_select_topk_workspace_bytes(int batch, int H, int W, int k);
 int dim_op_select_topk_f32(const float* nms, int batch, int H, int W, float threshold, const float* threshold_dev, int border, int k, int capacity,
                            int sort_always, int zero_fill, void* workspace, float* kpts_xy, float* scores, int32_t* n_out, int32_t* n_candidates,
                            void* stream);
+
+/* XFeat's selection (XFM:74-87) on caller-supplied maps: k1h [batch][H][W] (keypoint heat), h1 [batch][H/8][W/8] (reliability); H, W multiples of 8.
+ * candidate = k1h > threshold and no larger value in its 5 x 5 window (ONE pass: equal values are all kept); key = nearest(k1h) * bilinear(h1) through
+ * the reference's samplers (XFI), so the last row / column (nearest sample outside the map) and pixel (0, 0) (the padding position) have key 0 and are
+ * dropped like every key <= 0.  Then the chain of dim_op_select_topk_f32 on the key map with sort_always: the min(n, top_k) highest keys, descending.
+ * Outputs as there (scores = keys).  workspace: dim_op_xfeat_select_workspace_bytes(batch, H, W, top_k) bytes, 16-byte aligned.  top_k <= capacity <= 32768. */
+size_t dim_op_xfeat_select_workspace_bytes(int batch, int H, int W, int top_k);
+int dim_op_xfeat_select(const float* k1h, const float* h1, int batch, int H, int W, float threshold, int top_k, int capacity, void* workspace, float* kpts_xy,
+                        float* scores, int32_t* n_out, void* stream);
 
 /* SuperPoint's descriptor sampling (SPN:81-98,215; fix_sampling != 0: the variant of extractors/superpoint.py:16-27) as one kernel: the dense
  * map dense_nhwc [batch][h][w][256] (NOT normalised: every cell is L2-normalised on the fly, eps 1e-12) is sampled bilinearly (zero padding)
