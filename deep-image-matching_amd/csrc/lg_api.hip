@@ -11,21 +11,8 @@
 #include <vector>
 
 #include "../../include/dim_hip.h"
-#include "lg_kernels.h"
+#include "lg_handle.h"
 
-namespace {
-struct LayerW {
-  float *qkv_w, *qkv_b, *out_w, *out_b, *sffn0_w, *sffn0_b, *sln_w, *sln_b, *sffn3_w, *sffn3_b;
-  float *cqkv_w, *cqkv_b, *cout_w, *cout_b, *cffn0_w, *cffn0_b, *cln_w, *cln_b, *cffn3_w, *cffn3_b;
-  float *match_w, *match_b, *proj_w, *proj_b, *tok_w, *tok_b;
-  // pre-split copies of the GEMM operands for the split modes 1 (bf16x6) and 2 (fp16x3), gemm_x6.hip; index = mode
-  SplitWeights qkv_x[3], out_x[3], sffn0_x[3], sffn3_x[3], cqkv_x[3], cout_x[3], cffn0_x[3], cffn3_x[3], proj_x[3];
-  // out_proj folded into ffn.0 (split modes): [desc | ctx] * [W1a ; Wout*W1b] + (b1 + bout*W1b)
-  SplitWeights sffn0f_x[3], cffn0f_x[3];
-  SplitWeights sffn3p_x[3], cffn3p_x[3];   // ffn.3 with the k permutation of the fused feed-forward kernel (gemm_x6.hip, KV == 4)
-  float *sffn0f_b, *cffn0f_b;
-};
-}  // namespace
 
 constexpr int FOLLOW_MAX_PAIRS = 2;   // handles created for at most this many pairs may follow the stop flags on the host
 namespace {
@@ -76,21 +63,6 @@ __global__ __launch_bounds__(256) void lg_stage_kernel(StageArgs a) {
 }
 }  // namespace
 
-struct dim_lg {
-  DimHandleBase base;   // first member: dim_handle_tune_set
-  dim_lg_config cfg;
-  int n_layers, input_dim, max_pairs, nmax;
-  std::vector<LayerW> L;
-  std::vector<float> thr;
-  float *inproj_w, *inproj_b, *Wr;
-  // the deferred assignment of adaptive depth (dim_lg_match): per-layer tables the kernels index with a pair's stop layer
-  float *match_w_all = nullptr, *match_b_all = nullptr;   // [layers][256], [layers]
-  GemmLayerTab* proj_tab[3] = {nullptr, nullptr, nullptr};   // [mode][layers]: final_proj's split weights / inverse scales / bias
-  // adaptive depth at one or two pairs per call: the host follows the stop flags two layers behind the device (dim_lg_match)
-  int* done_host = nullptr;            // page-locked, device-mapped: [layers][max_pairs flags | sequence word] written by lg_decide_kernel
-  int call_seq = 0;
-  LgState st;
-};
 
 namespace {
 // [K][N] fp32 GEMM operand -> device split planes for both split modes
@@ -268,6 +240,9 @@ int dim_lg_match(dim_lg* h, const float* kpts_tab_dev, const float* desc_tab_dev
   DIM_REQUIRE(n_pairs >= 1 && n_pairs <= h->max_pairs, "dim_lg_match: n_pairs %d outside [1,%d]", n_pairs, h->max_pairs);
   DIM_REQUIRE(cap > 0, "dim_lg_match: cap");
   hipStream_t s = (hipStream_t)stream;
+  if (h->st.dim != 256)   // a LighterGlue handle (dim_lgl_create): the same call on the 96-wide kernels
+    return lgl_match(h, kpts_tab_dev, desc_tab_dev, n_tab_dev, size_tab_dev, cap, pair_idx_dev, n_pairs, matches_dev, mscores_dev, n_matches_dev,
+                     matches01_dev, mscores01_dev, stop_dev, prune01_dev, dense_scores_dev, s);
   LgState st = h->st;
   st.n_pairs = n_pairs; st.n_items = 2 * n_pairs;
   const int N = st.nmax, I = st.n_items, Lr = h->n_layers;

@@ -35,6 +35,10 @@ struct LgState {  // device pointers owned by the handle
   unsigned* sat_qkv = nullptr; unsigned* sat_ffn = nullptr;  // fp16x3 range-guard counters (dim_common.h), set per call
   int nsel = 0;   // upper bound of the live rows of any item in THIS call (<= nmax; dim_lg_match: the feature table's rows per image): launch shapes follow it, strides follow nmax
   float* attn_part; int attn_part_items;  // scratch of the key-split attention used for small batches ([items][4][nmax][4][68])
+  // width of the network: LightGlue 256 = 4 heads of 64 (everything above is written for it); LighterGlue 96 = 1 head of 96 (lgl_kernels.hip,
+  // lg_attn_d96.hip: desc / ctx / msg / md rows of 96, enc rows of 96 = cos[48] | sin[48], qkv rows of 288, hid rows of 192, kv_img
+  // [items][tiles][2304 x 16 B], attn_part [items][nmax][4][100])
+  int dim = 256, heads = 4, head_dim = 64;
 };
 
 int launch_lg_init(const LgState& st, const float* kpts_tab, const float* desc_tab, const int* n_tab, const float* size_tab,
@@ -55,3 +59,13 @@ int launch_lg_assign_argmax(const LgState& st, int tag, float* dense_scores, hip
 int launch_lg_finalize(const LgState& st, int n_layers, int prune_enabled, float filter_thr, int out_cap,
                        long long* matches, float* mscores, int* n_matches, int* mfull, float* msfull, int* stop,
                        int* prune_out, hipStream_t s);
+
+// ---- width 96, one head (LighterGlue): lgl_kernels.hip, lg_attn_d96.hip.  Same contracts as their 256-wide namesakes above; the kernels that only see
+// sim, counts and indices (decide, prune scan / commit, column stats, the argmax passes, finalize) serve both widths.
+int launch_lgl_init(const LgState& st, const float* kpts_tab, const int* n_tab, const float* size_tab, const int* pair_idx, int cap, const float* Wr, hipStream_t s);
+int launch_lgl_attention(const LgState& st, int cross, hipStream_t s);   // split modes only (dim_precision_mode() 1 | 2)
+int launch_lgl_ln_gelu(const LgState& st, const float* gamma, const float* beta, hipStream_t s);
+int launch_lgl_confidence(const LgState& st, const float* w_tok, const float* b_tok, const float* w_match, const float* b_match, float thr, int use_token, hipStream_t s);
+int launch_lgl_prune_move(const LgState& st, int pruning_min, hipStream_t s);   // the gather + copy-back passes between launch_lg_prune's scan and commit
+// md = final_proj(desc) / 96^0.25 in place for the pairs with done == tag (LGN:268-270; 96^0.25 is no power of two, so the weights cannot carry it)
+int launch_lgl_scale_md(const LgState& st, int tag, unsigned* sat, hipStream_t s);

@@ -273,19 +273,26 @@ __global__ void lg_prune_commit_kernel(LgState st, int layer) {
 // assignment (LGN:246-275): per-row / per-column softmax statistics of sim and the
 // log-sigmoid of the matchability logit, for pairs with done == tag.
 // side 0 rows: wave per row (coalesced along the row).
+// D: the descriptor width (256; 96 = LighterGlue, whose rows fill the first 24 lanes)
+template <int D>
+__device__ __forceinline__ void lg_row_load(const float* desc_row, const float* w_match, int lane, float4& d, float4& wm) {
+  if (D == 256 || lane * 4 < D) { d = *(const float4*)(desc_row + lane * 4); wm = *(const float4*)(w_match + lane * 4); }
+  else { d = make_float4(0.f, 0.f, 0.f, 0.f); wm = d; }
+}
+template <int D>
 __global__ __launch_bounds__(256) void lg_row_stats_kernel(LgState st, int tag, const float* __restrict__ w_match,
                                                            const float* __restrict__ b_match) {
   const int item = blockIdx.y, p = item >> 1, side = item & 1;
   const int dn = st.done[p];
   if (tag ? dn != tag : dn <= 0) return;   // tag 0: every stopped pair (its layer's weights: lg_api.hip, the deferred assignment)
-  if (tag == 0) { w_match += (size_t)(dn - 1) * 256; b_match += dn - 1; }   // [layers][256] / [layers] tables
+  if (tag == 0) { w_match += (size_t)(dn - 1) * D; b_match += dn - 1; }   // [layers][D] / [layers] tables
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int n = st.n_cur[item];
   if (row >= n) return;
   const size_t r = (size_t)item * st.nmax + row;
   // logsigmoid(matchability logit) for this point (both sides)
-  const float4 d = *(const float4*)(st.desc + r * 256 + lane * 4);
-  const float4 wm = *(const float4*)(w_match + lane * 4);
+  float4 d, wm;
+  lg_row_load<D>(st.desc + r * D, w_match, lane, d, wm);
   const float z = wave_sum(d.x * wm.x + d.y * wm.y + d.z * wm.z + d.w * wm.w) + b_match[0];
   if (lane == 0) st.zls[r] = logsigmoidf_(z);
   if (side != 0) return;
@@ -510,8 +517,12 @@ int launch_lg_prune(const LgState& st, int layer, double width_conf, float thr, 
                     hipStream_t s) {
   const float keep_thr = (float)(1.0 - width_conf);  // python double, cast to the tensor dtype at the compare (LGN:588)
   hipLaunchKernelGGL(lg_prune_scan_kernel, dim3(st.n_items), dim3(1024), 0, s, st, keep_thr, thr, use_token, pruning_min);
-  hipLaunchKernelGGL(lg_prune_gather_kernel, dim3(cdiv(st.nmax, 4), st.n_items), dim3(256), 0, s, st, pruning_min);
-  hipLaunchKernelGGL(lg_prune_copyback_kernel, dim3(cdiv(st.nmax, 4), st.n_items), dim3(256), 0, s, st, pruning_min);
+  if (st.dim != 256) {   // the two passes that move descriptor and encoding rows: their 96-wide forms (lgl_kernels.hip)
+    if (launch_lgl_prune_move(st, pruning_min, s) != 0) return -1;
+  } else {
+    hipLaunchKernelGGL(lg_prune_gather_kernel, dim3(cdiv(st.nmax, 4), st.n_items), dim3(256), 0, s, st, pruning_min);
+    hipLaunchKernelGGL(lg_prune_copyback_kernel, dim3(cdiv(st.nmax, 4), st.n_items), dim3(256), 0, s, st, pruning_min);
+  }
   hipLaunchKernelGGL(lg_prune_commit_kernel, dim3(cdiv(st.n_pairs, 64)), dim3(64), 0, s, st, layer);
   DIM_LAUNCH_CHECK();
   return 0;
@@ -523,19 +534,19 @@ int launch_lg_prune(const LgState& st, int layer, double width_conf, float thr, 
 // 6-instruction exp_le0 (dim_common.h, ~1.5 ulp). ----
 constexpr int ROW_CH_MAX = 16;   // float4 chunks per lane: 64 lanes x 4 x 16 = 4096 columns (8 for rows of up to 2048)
 __device__ __forceinline__ float exp_le0_z(float d) { return d > -INFINITY ? exp_le0(d) : 0.0f; }   // exp(d), d <= 0, with exp(-inf) = 0 (exp_le0 itself returns NaN there)
-template <int ROW_CH>   // float4 chunks per lane: 8 = rows of up to 2048 live columns, 16 = up to 4096 (round 6: a 2100-keypoint pair fell to the generic kernels)
+template <int ROW_CH, int D = 256>   // float4 chunks per lane: 8 = rows of up to 2048 live columns, 16 = up to 4096 (round 6: a 2100-keypoint pair fell to the generic kernels)
 __global__ __launch_bounds__(256) void lg_row_stats4_kernel(LgState st, int tag, const float* __restrict__ w_match,
                                                             const float* __restrict__ b_match) {
   const int item = blockIdx.y, p = item >> 1, side = item & 1;
   const int dn = st.done[p];
   if (tag ? dn != tag : dn <= 0) return;   // tag 0: every stopped pair (its layer's weights: lg_api.hip, the deferred assignment)
-  if (tag == 0) { w_match += (size_t)(dn - 1) * 256; b_match += dn - 1; }   // [layers][256] / [layers] tables
+  if (tag == 0) { w_match += (size_t)(dn - 1) * D; b_match += dn - 1; }   // [layers][D] / [layers] tables
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int n = st.n_cur[item];
   if (row >= n) return;
   const size_t r = (size_t)item * st.nmax + row;
-  const float4 d = *(const float4*)(st.desc + r * 256 + lane * 4);
-  const float4 wm = *(const float4*)(w_match + lane * 4);
+  float4 d, wm;
+  lg_row_load<D>(st.desc + r * D, w_match, lane, d, wm);
   const float z = wave_sum(d.x * wm.x + d.y * wm.y + d.z * wm.z + d.w * wm.w) + b_match[0];
   if (lane == 0) st.zls[r] = logsigmoidf_(z);
   if (side != 0) return;
@@ -701,13 +712,16 @@ static bool assign_rows_2048(const LgState& st) { return (st.nsel > 0 ? st.nsel 
 
 int launch_lg_assign_stats(const LgState& st, int tag, const float* w_match, const float* b_match, hipStream_t s) {
   if (assign_fast_shape(st)) {
-    if (assign_rows_2048(st)) hipLaunchKernelGGL(HIP_KERNEL_NAME(lg_row_stats4_kernel<8>), dim3(cdiv(st.nmax, 4), st.n_items), dim3(256), 0, s, st, tag, w_match, b_match);
+    if (st.dim == 96 && assign_rows_2048(st)) hipLaunchKernelGGL(HIP_KERNEL_NAME(lg_row_stats4_kernel<8, 96>), dim3(cdiv(st.nmax, 4), st.n_items), dim3(256), 0, s, st, tag, w_match, b_match);
+    else if (st.dim == 96) hipLaunchKernelGGL(HIP_KERNEL_NAME(lg_row_stats4_kernel<16, 96>), dim3(cdiv(st.nmax, 4), st.n_items), dim3(256), 0, s, st, tag, w_match, b_match);
+    else if (assign_rows_2048(st)) hipLaunchKernelGGL(HIP_KERNEL_NAME(lg_row_stats4_kernel<8>), dim3(cdiv(st.nmax, 4), st.n_items), dim3(256), 0, s, st, tag, w_match, b_match);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(lg_row_stats4_kernel<16>), dim3(cdiv(st.nmax, 4), st.n_items), dim3(256), 0, s, st, tag, w_match, b_match);
     hipLaunchKernelGGL(lg_col_stats4_kernel, dim3(cdiv(st.nmax, 4 * COL_CW), st.n_pairs), dim3(1024), 0, s, st, tag);
     DIM_LAUNCH_CHECK();
     return 0;
   }
-  hipLaunchKernelGGL(lg_row_stats_kernel, dim3(cdiv(st.nmax, 4), st.n_items), dim3(256), 0, s, st, tag, w_match, b_match);
+  if (st.dim == 96) hipLaunchKernelGGL(HIP_KERNEL_NAME(lg_row_stats_kernel<96>), dim3(cdiv(st.nmax, 4), st.n_items), dim3(256), 0, s, st, tag, w_match, b_match);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(lg_row_stats_kernel<256>), dim3(cdiv(st.nmax, 4), st.n_items), dim3(256), 0, s, st, tag, w_match, b_match);
   hipLaunchKernelGGL(lg_col_stats_kernel, dim3(cdiv(st.nmax, 64), st.n_pairs), dim3(1024), 0, s, st, tag);
   DIM_LAUNCH_CHECK();
   return 0;

@@ -53,6 +53,7 @@ class LightGlueHIP(capi.ResidentHandle):
     _destroy = "dim_lg_destroy"
     default_conf = {"n_layers": 9, "depth_confidence": 0.95, "width_confidence": 0.99, "filter_threshold": 0.1,
                     "pruning_min_kpts": -1}
+    descriptor_dim = 256   # width of the network's state; input_proj exists iff the input width differs (LGN:361-364)
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], conf: Optional[dict] = None, max_pairs: int = 1,
                  max_kpts: int = 2048, device="cuda", lib=None, on_saturation: str = "fallback", arithmetic=None):
@@ -60,7 +61,7 @@ class LightGlueHIP(capi.ResidentHandle):
         self._open(device, lib, on_saturation, arithmetic)
         L = int(self.conf["n_layers"])
         host = lambda name: self._host(state_dict[name])
-        self.input_dim = int(state_dict["input_proj.weight"].shape[1]) if "input_proj.weight" in state_dict else 256
+        self.input_dim = int(state_dict["input_proj.weight"].shape[1]) if "input_proj.weight" in state_dict else self.descriptor_dim
         layers = (_LgLayer * L)()
         for i in range(L):
             for field, key in _LAYER_FIELDS:
@@ -68,16 +69,19 @@ class LightGlueHIP(capi.ResidentHandle):
                 setattr(layers[i], field, host(k) if k in state_dict else None)
         w = _LgWeights()
         w.n_layers, w.input_dim = L, self.input_dim
-        w.input_proj_w = host("input_proj.weight") if self.input_dim != 256 else None
-        w.input_proj_b = host("input_proj.bias") if self.input_dim != 256 else None
+        w.input_proj_w = host("input_proj.weight") if self.input_dim != self.descriptor_dim else None
+        w.input_proj_b = host("input_proj.bias") if self.input_dim != self.descriptor_dim else None
         w.posenc_Wr = host("posenc.Wr.weight")
         w.confidence_thresholds = host("confidence_thresholds")
         w.layers = layers
         c = _LgConfig(float(self.conf["depth_confidence"]), float(self.conf["width_confidence"]),
                       float(self.conf["filter_threshold"]), int(self.conf["pruning_min_kpts"]))
         self.max_pairs = int(max_pairs)
-        self._create(self.lib.dim_lg_create, ctypes.byref(w), ctypes.byref(c), self.max_pairs, int(max_kpts))
+        self._create_handle(w, c, int(max_kpts))
         self.nk = self.lib.dim_lg_max_kpts(self._h)
+
+    def _create_handle(self, w, c, max_kpts):
+        self._create(self.lib.dim_lg_create, ctypes.byref(w), ctypes.byref(c), self.max_pairs, max_kpts)
 
     def match_batch_guarded(self, *a, logger=None, **k):
         """match_batch under the fp16x3 range guard (capi.run_guarded): synchronises."""

@@ -11,7 +11,8 @@ matcher_base.py:36-60); otherwise a minimal stand-in base with the same construc
 (extractor_base.py:119-160) is used so the hooks can be driven and tested on their own.
 ``KorniaMatcher`` mirrors matchers/kornia_matcher.py:9-53 (nearest-neighbour descriptor matching, no weights);
 ``SuperPointOpenExtractor`` mirrors extractors/superpoint_open.py:72-164 (the openly licensed SuperPoint);
-``XfeatExtractor`` mirrors extractors/xfeat.py:11-63 (XFeat's sparse detectAndCompute).
+``XfeatExtractor`` mirrors extractors/xfeat.py:11-63 (XFeat's sparse detectAndCompute);
+``LighterGlueMatcher`` mirrors matchers/lighterglue.py:78-241 (the matcher of the shipped ``xfeat+lighterglue`` pipeline).
 See INTEGRATION.md for the module files a maintainer adds to the reference tree.
 """
 from __future__ import annotations
@@ -29,6 +30,7 @@ from . import weights as _weights
 from .alike_hip import AlikeHIP
 from .aliked_hip import AlikedHIP
 from .lightglue_hip import LightGlueHIP
+from .lighterglue_hip import LighterGlueHIP
 from .nn_hip import NearestNeighborHIP, check_mode as _check_nn_mode
 from .superpoint_hip import SuperPointHIP, SuperPointOpenHIP
 from .tile_matching import BatchedTileMatchingMixin
@@ -631,53 +633,13 @@ class _ResidentMatcherMixin:
         return res[2:2 + 2 * S].reshape(S, 2).copy()
 
 
-class LightGlueMatcher(_ResidentMatcherMixin, BatchedTileMatchingMixin, _MatcherBase):
-    """matchers/lightglue.py:77 — LightGlue on the gfx950 library."""
+class _LightGluePairMixin(_ResidentMatcherMixin):
+    """The per-pair hook LightGlueMatcher and LighterGlueMatcher share: features.h5's arrays -> one call on the resident ``self._net`` (a LightGlueHIP
+    or a subclass of it, from the matcher's ``_new_net``), staged with one upload and one download on a GPU.  ``_stage_tag`` names the matcher's
+    page-locked buffers, ``_what`` is its name in the range guard's log lines."""
 
-    _default_conf = {
-        "flash": True,   # accepted for compatibility; attention here is always the flash-attention kernel of lg_attn_x6.hip (fp16x3 / bf16x6 split arithmetic, lg_attn.hip in fp32 MFMA mode)
-        "mp": False,
-        "depth_confidence": 0.95,
-        "width_confidence": 0.99,
-        "filter_threshold": 0.1,
-        "weights": None,
-        # LGN:318-323,606-610: below this many keypoints the reference does not prune.  "auto" = what the reference
-        # uses on a GPU (1536 with flash attention, 1024 without); -1 = its CPU behaviour (always prune), which is
-        # what the CPU-generated parity goldens need.
-        "pruning_min_kpts": "auto",
-    }
-    required_inputs = []
-    min_matches = 20
-    max_feat_no_tiling = 200000
-    _input_dims = {"superpoint": 256, "disk": 128, "aliked": 128, "sift": 128}  # LGN:331-349
-
-    def __init__(self, config, local_features="superpoint") -> None:
-        self._localfeatures = local_features
-        super().__init__(config)
-        self._lib = capi.load()
-        self._device = _resolve_device(self._device, "LightGlueMatcher")
-        cfg = {**self._default_conf, **self.config.get("matcher", {})}
-        self._arith = _apply_arithmetic(cfg, self._lib)
-        self._on_sat = _saturation_policy(cfg)
-        if cfg.get("mp"):
-            logger.warning("LightGlue: mixed precision ('mp') is not implemented on the MI355X path; running fp32")
-        self._conf = {k: cfg[k] for k in ("depth_confidence", "width_confidence", "filter_threshold")}
-        self._conf["n_layers"] = int(cfg.get("n_layers", 9))
-        pm = cfg.get("pruning_min_kpts", "auto")
-        self._conf["pruning_min_kpts"] = (1536 if cfg.get("flash", True) else 1024) if pm == "auto" else int(pm)
-        path = cfg.get("weights_path") or os.environ.get("DIM_LIGHTGLUE_WEIGHTS")
-        in_dim = self._input_dims.get(local_features, 256)
-        if path is None and cfg.get("allow_synthetic_weights"):
-            logger.warning("LightGlue: running on seeded SYNTHETIC weights (allow_synthetic_weights) - test / benchmark use only")
-        self._sd = _weights.load_lightglue_state_dict(path, input_dim=in_dim, n_layers=self._conf["n_layers"],
-                                                      allow_synthetic=bool(cfg.get("allow_synthetic_weights", False)))
-        self._net: Optional[LightGlueHIP] = None
-        self._net_n = 0
-        if self._localfeatures == "disk":
-            self.max_feat_no_tiling = 50000
-
-    def _new_net(self, pairs: int, n: int) -> LightGlueHIP:
-        return LightGlueHIP(self._sd, self._conf, max_pairs=pairs, max_kpts=n, device=self._dev(), lib=self._lib, on_saturation=self._on_sat, arithmetic=self._arith)
+    _stage_tag = "lg"
+    _what = "LightGlue"
 
     @torch.no_grad()
     def _match_pairs(self, feats0: dict, feats1: dict) -> np.ndarray:
@@ -742,7 +704,7 @@ class LightGlueMatcher(_ResidentMatcherMixin, BatchedTileMatchingMixin, _Matcher
         NK = net.nk
         f16 = lambda a: int(a.dtype == np.float16)
         return self._match_one_pair(
-            "lg", "LightGlue",
+            self._stage_tag, self._what,
             [(0, np.concatenate([size_of(f0, k0), size_of(f1, k1)]).astype(np.float32)), (16, np.array((m, n), dtype=np.int32))],   # [sizes 4 f32 | counts 2 i32 | pad]
             (k0, d0, k1, d1),
             lambda base, offs: [capi.LgRawFeatures(base + offs[0], base + offs[1], m, f16(k0), f16(d0), dn0), capi.LgRawFeatures(base + offs[2], base + offs[3], n, f16(k1), f16(d1), dn1)],
@@ -750,6 +712,132 @@ class LightGlueMatcher(_ResidentMatcherMixin, BatchedTileMatchingMixin, _Matcher
             lambda NK, dev: {"matches01": torch.zeros(1, 2, NK, dtype=torch.int32, device=dev), "mscores01": torch.zeros(1, 2, NK, dtype=torch.float32, device=dev),
                              "stop": torch.zeros(1, dtype=torch.int32, device=dev), "prune01": torch.zeros(1, 2, NK, dtype=torch.int32, device=dev)},
             lambda kt, dt, rawd, out: net.match_batch(kt, dt, rawd[16:24].view(torch.int32), rawd[:16].view(torch.float32).view(2, 2), n_pairs=1, out=out))
+
+
+class LightGlueMatcher(_LightGluePairMixin, BatchedTileMatchingMixin, _MatcherBase):
+    """matchers/lightglue.py:77 — LightGlue on the gfx950 library."""
+
+    _default_conf = {
+        "flash": True,   # accepted for compatibility; attention here is always the flash-attention kernel of lg_attn_x6.hip (fp16x3 / bf16x6 split arithmetic, lg_attn.hip in fp32 MFMA mode)
+        "mp": False,
+        "depth_confidence": 0.95,
+        "width_confidence": 0.99,
+        "filter_threshold": 0.1,
+        "weights": None,
+        # LGN:318-323,606-610: below this many keypoints the reference does not prune.  "auto" = what the reference
+        # uses on a GPU (1536 with flash attention, 1024 without); -1 = its CPU behaviour (always prune), which is
+        # what the CPU-generated parity goldens need.
+        "pruning_min_kpts": "auto",
+    }
+    required_inputs = []
+    min_matches = 20
+    max_feat_no_tiling = 200000
+    _input_dims = {"superpoint": 256, "disk": 128, "aliked": 128, "sift": 128}  # LGN:331-349
+
+    def __init__(self, config, local_features="superpoint") -> None:
+        self._localfeatures = local_features
+        super().__init__(config)
+        self._lib = capi.load()
+        self._device = _resolve_device(self._device, "LightGlueMatcher")
+        cfg = {**self._default_conf, **self.config.get("matcher", {})}
+        self._arith = _apply_arithmetic(cfg, self._lib)
+        self._on_sat = _saturation_policy(cfg)
+        if cfg.get("mp"):
+            logger.warning("LightGlue: mixed precision ('mp') is not implemented on the MI355X path; running fp32")
+        self._conf = {k: cfg[k] for k in ("depth_confidence", "width_confidence", "filter_threshold")}
+        self._conf["n_layers"] = int(cfg.get("n_layers", 9))
+        pm = cfg.get("pruning_min_kpts", "auto")
+        self._conf["pruning_min_kpts"] = (1536 if cfg.get("flash", True) else 1024) if pm == "auto" else int(pm)
+        path = cfg.get("weights_path") or os.environ.get("DIM_LIGHTGLUE_WEIGHTS")
+        in_dim = self._input_dims.get(local_features, 256)
+        if path is None and cfg.get("allow_synthetic_weights"):
+            logger.warning("LightGlue: running on seeded SYNTHETIC weights (allow_synthetic_weights) - test / benchmark use only")
+        self._sd = _weights.load_lightglue_state_dict(path, input_dim=in_dim, n_layers=self._conf["n_layers"],
+                                                      allow_synthetic=bool(cfg.get("allow_synthetic_weights", False)))
+        self._net: Optional[LightGlueHIP] = None
+        self._net_n = 0
+        if self._localfeatures == "disk":
+            self.max_feat_no_tiling = 50000
+
+    def _new_net(self, pairs: int, n: int) -> LightGlueHIP:
+        return LightGlueHIP(self._sd, self._conf, max_pairs=pairs, max_kpts=n, device=self._dev(), lib=self._lib, on_saturation=self._on_sat, arithmetic=self._arith)
+
+
+class LighterGlueMatcher(_LightGluePairMixin, _MatcherBase):
+    """matchers/lighterglue.py:78 — LighterGlue (LightGlue at 64 -> 96, one head, 6 layers) on the gfx950 library, quirks included:
+    only ``local_features == "xfeat"``; the NETWORK's depth / width confidence are its own fixed (-1, 0.95) whatever the matcher config says (the
+    reference never hands them on, matchers/lighterglue.py:102,222); ``filter_threshold`` is read from the config at every call (:221);
+    ``image_size`` (H, W) reaches the network as (W, H) (:205-207 — LightGlueMatcher feeds (H, W)); a missing ``image_size`` is a ValueError (:193);
+    the result is an (S, 2) int32 array (:241).  No BatchedTileMatchingMixin: the tile loop hands no ``image_size`` on, which this matcher
+    refuses, so the reference's per-pair tile loop applies as it is."""
+
+    _default_conf = {
+        "flash": True,   # accepted for compatibility: attention is always the flash-attention kernel of lg_attn_d96.hip
+        "mp": False,
+        "depth_confidence": 0.95,   # (ignored, as in the reference)
+        "width_confidence": 0.99,   # (ignored, as in the reference)
+        "filter_threshold": 0.1,
+        "weights": None,
+        "pruning_min_kpts": "auto",   # as LightGlueMatcher: "auto" = the reference's GPU value, -1 = its CPU behaviour (always prune)
+    }
+    required_inputs = []
+    min_matches = 20
+    max_feat_no_tiling = 200000
+    _stage_tag = "lgl"
+    _what = "LighterGlue"
+    # thirdparty/accelerated_features/modules/lighterglue.py:12-27: what LightGlue(None) is built with
+    _network_conf = {"n_layers": 6, "depth_confidence": -1, "width_confidence": 0.95}
+
+    def __init__(self, config, local_features="superpoint") -> None:
+        self._localfeatures = local_features
+        super().__init__(config)
+        if self._localfeatures != "xfeat":
+            raise ValueError(f"Unsupported local feature extractor: {self._localfeatures}")
+        self._lib = capi.load()
+        self._device = _resolve_device(self._device, "LighterGlueMatcher")
+        cfg = {**self._default_conf, **self.config.get("matcher", {})}
+        self._arith = _apply_arithmetic(cfg, self._lib)
+        self._on_sat = _saturation_policy(cfg)
+        if cfg.get("mp"):
+            logger.warning("LighterGlue: mixed precision ('mp') is not implemented on the MI355X path; running the split fp32-class arithmetic")
+        pm = cfg.get("pruning_min_kpts", "auto")
+        self._conf = {**self._network_conf, "filter_threshold": float(cfg["filter_threshold"]),
+                      "pruning_min_kpts": (1536 if cfg.get("flash", True) else 1024) if pm == "auto" else int(pm)}
+        path = cfg.get("weights_path")
+        if path is None and not os.environ.get("DIM_LIGHTERGLUE_WEIGHTS") and cfg.get("allow_synthetic_weights"):
+            logger.warning("LighterGlue: running on seeded SYNTHETIC weights (allow_synthetic_weights) - test / benchmark use only")
+        self._sd = _weights.load_lighterglue_state_dict(path, allow_synthetic=bool(cfg.get("allow_synthetic_weights", False)))
+        self._net: Optional[LighterGlueHIP] = None
+        self._net_n = 0
+
+    def _new_net(self, pairs: int, n: int) -> LighterGlueHIP:
+        return LighterGlueHIP(self._sd, self._conf, max_pairs=pairs, max_kpts=n, device=self._dev(), lib=self._lib, on_saturation=self._on_sat, arithmetic=self._arith)
+
+    def _stale(self, net) -> bool:
+        """The threshold lives in the handle: a call with another ``filter_threshold`` in the config gets a new one."""
+        self._conf["filter_threshold"] = float(self.config["matcher"]["filter_threshold"])
+        return float(net.conf["filter_threshold"]) != self._conf["filter_threshold"]
+
+    @staticmethod
+    def _size_as_the_network_sees_it(f: dict) -> np.ndarray:
+        """matchers/lighterglue.py:174-207: unwrap, int32, float32, (H, W) -> (W, H)."""
+        s = f["image_size"]
+        if isinstance(s, (list, tuple)):
+            s = s[0]
+        if isinstance(s, torch.Tensor):
+            s = s.cpu().numpy()
+        s = np.asarray(s, dtype=np.int32).astype(np.float32).reshape(-1)
+        return np.array([s[1], s[0]], dtype=np.float32)
+
+    @torch.no_grad()
+    def _match_pairs(self, feats0: dict, feats1: dict) -> np.ndarray:
+        """feats: numpy dicts as read from features.h5 (keypoints (N, 2), descriptors (N, 64) or (64, N), float16 or float32, image_size (H, W)).
+        Returns (S, 2) int32 index pairs."""
+        if "image_size" not in feats0 or "image_size" not in feats1:
+            raise ValueError("image_size not found in features - required by XFeat's match_lighterglue")
+        f0 = {**feats0, "image_size": self._size_as_the_network_sees_it(feats0)}
+        f1 = {**feats1, "image_size": self._size_as_the_network_sees_it(feats1)}
+        return super()._match_pairs(f0, f1).astype(np.int32)
 
 
 class KorniaMatcher(_ResidentMatcherMixin, BatchedTileMatchingMixin, _MatcherBase):

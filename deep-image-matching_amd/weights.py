@@ -74,7 +74,7 @@ def lightglue_confidence_thresholds(n_layers: int = 9) -> torch.Tensor:
 
 
 def synthetic_lightglue_state_dict(seed: int = 0, input_dim: int = 256, n_layers: int = 9, dim: int = 256,
-                                   gain: float = 1.0) -> Dict[str, torch.Tensor]:
+                                   gain: float = 1.0, num_heads: int = 4) -> Dict[str, torch.Tensor]:
     """nn.Linear-style uniform init in the official key layout (LGN:361-378).
 
     ``gain`` > 1 sharpens the synthetic network (larger logits) so that softmaxes are
@@ -92,7 +92,7 @@ def synthetic_lightglue_state_dict(seed: int = 0, input_dim: int = 256, n_layers
     sd["confidence_thresholds"] = lightglue_confidence_thresholds(n_layers)
     if input_dim != dim:
         sd.update(lin(dim, input_dim, prefix="input_proj."))
-    sd["posenc.Wr.weight"] = torch.randn(dim // 4 // 2, 2, generator=g)  # head_dim//2 x 2, std gamma^-2 = 1 (LGN:62-63)
+    sd["posenc.Wr.weight"] = torch.randn(dim // num_heads // 2, 2, generator=g)  # head_dim//2 x 2, std gamma^-2 = 1 (LGN:62-63)
     for i in range(n_layers):
         t = f"transformers.{i}."
         sd.update(lin(3 * dim, dim, prefix=t + "self_attn.Wqkv."))
@@ -113,7 +113,8 @@ def synthetic_lightglue_state_dict(seed: int = 0, input_dim: int = 256, n_layers
 
 def synthetic_lightglue_matching_state_dict(seed: int = 0, input_dim: int = 256, n_layers: int = 9, dim: int = 256,
                                             residual: float = 0.003, sharpness: float = 220.0, matchability_bias: float = 5.0,
-                                            center: Optional[torch.Tensor] = None, whiten: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                                            center: Optional[torch.Tensor] = None, whiten: Optional[torch.Tensor] = None,
+                                            num_heads: int = 4) -> Dict[str, torch.Tensor]:
     """Seeded synthetic LightGlue weights (official key layout) that MATCH: the transformer blocks are near-identity (`ffn.3`
     scaled by ``residual``, so a keypoint's state stays close to its input descriptor), every `final_proj` is
     ``sharpness`` x (identity - ``center``) (an orthogonal map: the similarity is sharpness^2 / 16 x the inner product of the CENTRED
@@ -128,7 +129,7 @@ def synthetic_lightglue_matching_state_dict(seed: int = 0, input_dim: int = 256,
     DIFFERENT photographs share no equal descriptors, and in the plain centred dot product a few long descriptors are everyone's nearest
     neighbour (20 - 41 mutual nearest neighbours among 2000 x 2000 keypoints of the DSC photographs under the seeded SuperPoint); after whitening
     the similarity is a Mahalanobis one and 216 - 406 are mutual (sharpness 2: 132 - 180 matches above 0.1, logits <= 220)."""
-    sd = synthetic_lightglue_state_dict(seed, input_dim, n_layers, dim, gain=1.0)
+    sd = synthetic_lightglue_state_dict(seed, input_dim, n_layers, dim, gain=1.0, num_heads=num_heads)
     for k in list(sd):
         if ".ffn.3." in k:
             sd[k] = sd[k] * residual
@@ -166,6 +167,65 @@ def load_lightglue_state_dict(path: str | None = None, seed: int = 0, input_dim:
     if "confidence_thresholds" not in sd:
         sd["confidence_thresholds"] = lightglue_confidence_thresholds(n_layers)
     return {k: v.float().contiguous() for k, v in sd.items()}
+
+
+LIGHTERGLUE_SHAPE = {"input_dim": 64, "descriptor_dim": 96, "num_heads": 1, "n_layers": 6}   # modules/lighterglue.py:12-27
+
+
+def lighterglue_state_dict_shapes(input_dim: int = 64, dim: int = 96, n_layers: int = 6, num_heads: int = 1) -> Dict[str, tuple]:
+    """Every tensor LighterGlueHIP reads, by its official (renamed) key."""
+    sh = {"input_proj.weight": (dim, input_dim), "input_proj.bias": (dim,), "posenc.Wr.weight": (dim // num_heads // 2, 2)}
+    for i in range(n_layers):
+        t = f"transformers.{i}."
+        sh.update({t + "self_attn.Wqkv.weight": (3 * dim, dim), t + "self_attn.Wqkv.bias": (3 * dim,),
+                   t + "self_attn.out_proj.weight": (dim, dim), t + "self_attn.out_proj.bias": (dim,)})
+        for blk in ("self_attn", "cross_attn"):
+            sh.update({t + blk + ".ffn.0.weight": (2 * dim, 2 * dim), t + blk + ".ffn.0.bias": (2 * dim,), t + blk + ".ffn.1.weight": (2 * dim,),
+                       t + blk + ".ffn.1.bias": (2 * dim,), t + blk + ".ffn.3.weight": (dim, 2 * dim), t + blk + ".ffn.3.bias": (dim,)})
+        for nm in ("to_qk", "to_v", "to_out"):
+            sh.update({t + f"cross_attn.{nm}.weight": (dim, dim), t + f"cross_attn.{nm}.bias": (dim,)})
+        sh.update({f"log_assignment.{i}.matchability.weight": (1, dim), f"log_assignment.{i}.matchability.bias": (1,),
+                   f"log_assignment.{i}.final_proj.weight": (dim, dim), f"log_assignment.{i}.final_proj.bias": (dim,)})
+        if i < n_layers - 1:
+            sh.update({f"token_confidence.{i}.token.0.weight": (1, dim), f"token_confidence.{i}.token.0.bias": (1,)})
+    return sh
+
+
+def validate_lighterglue_state_dict(sd: Dict[str, torch.Tensor]) -> None:
+    for k, shape in lighterglue_state_dict_shapes().items():
+        if k not in sd:
+            raise KeyError(f"LighterGlue checkpoint lacks '{k}'")
+        if tuple(sd[k].shape) != shape:
+            raise ValueError(f"LighterGlue checkpoint: '{k}' has shape {tuple(sd[k].shape)}, expected {shape}")
+
+
+def synthetic_lighterglue_state_dict(seed: int = 0, matching: bool = True, **kw) -> Dict[str, torch.Tensor]:
+    """Seeded synthetic weights at LighterGlue's shape (64 -> 96, one head, 6 layers): the matching kind by default."""
+    shape = dict(input_dim=64, n_layers=6, dim=96, num_heads=1)
+    if matching:
+        return synthetic_lightglue_matching_state_dict(seed, **shape, **kw)
+    return synthetic_lightglue_state_dict(seed, **shape, **kw)
+
+
+def load_lighterglue_state_dict(path: str | None = None, seed: int = 0, allow_synthetic: bool = False) -> Dict[str, torch.Tensor]:
+    """xfeat-lighterglue.pt with the reference's key renames (modules/lighterglue.py:41-46: `matcher.` stripped, self_attn.{i} / cross_attn.{i}
+    -> transformers.{i}.*), shapes validated.  ``path`` None: the DIM_LIGHTERGLUE_WEIGHTS environment variable, else (opt-in) synthetic weights."""
+    import os
+
+    path = path or os.environ.get("DIM_LIGHTERGLUE_WEIGHTS") or None
+    if path is None:
+        _no_weights("LighterGlue (xfeat-lighterglue.pt, modules/lighterglue.py:33-37)", "DIM_LIGHTERGLUE_WEIGHTS", allow_synthetic)
+        return synthetic_lighterglue_state_dict(seed)
+    sd = torch.load(str(Path(path)), map_location="cpu")
+    for i in range(LIGHTERGLUE_SHAPE["n_layers"]):
+        sd = {k.replace(f"self_attn.{i}", f"transformers.{i}.self_attn"): v for k, v in sd.items()}
+        sd = {k.replace(f"cross_attn.{i}", f"transformers.{i}.cross_attn"): v for k, v in sd.items()}
+        sd = {k.replace("matcher.", ""): v for k, v in sd.items()}
+    if "confidence_thresholds" not in sd:
+        sd["confidence_thresholds"] = lightglue_confidence_thresholds(LIGHTERGLUE_SHAPE["n_layers"])
+    sd = {k: v.float().contiguous() for k, v in sd.items()}
+    validate_lighterglue_state_dict(sd)
+    return sd
 
 
 ALIKED_CFGS = {  # ALN:573-579  c1, c2, c3, c4, dim, K, M

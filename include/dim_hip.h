@@ -317,27 +317,28 @@ int dim_xfeat_debug_buffers(dim_xfeat* h, const float** norm_image, const float*
 /* ------------------------------------------------------------------------ */
 
 /* Per-layer tensors in the reference's state_dict layout (nn.Linear weight
- * [out][in], LGN:361-378), host pointers. */
+ * [out][in], LGN:361-378), host pointers.  d = descriptor_dim, hd = d / heads: 256 and 64 for
+ * dim_lg_create (LightGlue), 96 and 96 for dim_lgl_create (LighterGlue). */
 typedef struct dim_lg_layer_weights {
-  const float *self_Wqkv_w, *self_Wqkv_b;   /* transformers.i.self_attn.Wqkv   (768,256) rows = head*192+dim*3+{q,k,v} */
-  const float *self_out_w, *self_out_b;     /* transformers.i.self_attn.out_proj (256,256) */
-  const float *self_ffn0_w, *self_ffn0_b;   /* ...self_attn.ffn.0 (512,512) */
-  const float *self_ln_w, *self_ln_b;       /* ...self_attn.ffn.1 LayerNorm(512) */
-  const float *self_ffn3_w, *self_ffn3_b;   /* ...self_attn.ffn.3 (256,512) */
-  const float *cross_qk_w, *cross_qk_b;     /* transformers.i.cross_attn.to_qk (256,256) */
+  const float *self_Wqkv_w, *self_Wqkv_b;   /* transformers.i.self_attn.Wqkv   (3d,d) rows = head*3hd+dim*3+{q,k,v} */
+  const float *self_out_w, *self_out_b;     /* transformers.i.self_attn.out_proj (d,d) */
+  const float *self_ffn0_w, *self_ffn0_b;   /* ...self_attn.ffn.0 (2d,2d) */
+  const float *self_ln_w, *self_ln_b;       /* ...self_attn.ffn.1 LayerNorm(2d) */
+  const float *self_ffn3_w, *self_ffn3_b;   /* ...self_attn.ffn.3 (d,2d) */
+  const float *cross_qk_w, *cross_qk_b;     /* transformers.i.cross_attn.to_qk (d,d) */
   const float *cross_v_w, *cross_v_b;       /* ...to_v */
   const float *cross_out_w, *cross_out_b;   /* ...to_out */
   const float *cross_ffn0_w, *cross_ffn0_b, *cross_ln_w, *cross_ln_b, *cross_ffn3_w, *cross_ffn3_b;
-  const float *assign_match_w, *assign_match_b; /* log_assignment.i.matchability (1,256),(1,) */
-  const float *assign_proj_w, *assign_proj_b;   /* log_assignment.i.final_proj (256,256) */
-  const float *token_w, *token_b;               /* token_confidence.i.token.0 (1,256),(1,); NULL for the last layer */
+  const float *assign_match_w, *assign_match_b; /* log_assignment.i.matchability (1,d),(1,) */
+  const float *assign_proj_w, *assign_proj_b;   /* log_assignment.i.final_proj (d,d) */
+  const float *token_w, *token_b;               /* token_confidence.i.token.0 (1,d),(1,); NULL for the last layer */
 } dim_lg_layer_weights;
 
 typedef struct dim_lg_weights {
-  int n_layers;                       /* 9 */
-  int input_dim;                      /* 256 (SuperPoint) or 128 (ALIKED/DISK/SIFT) */
-  const float *input_proj_w, *input_proj_b; /* (256,input_dim),(256,) or NULL when input_dim == 256 (LGN:361-364) */
-  const float* posenc_Wr;             /* posenc.Wr.weight (32,2) */
+  int n_layers;                       /* 9 (LighterGlue: 6) */
+  int input_dim;                      /* 256 (SuperPoint), 128 (ALIKED/DISK/SIFT) or 64 (XFeat, LighterGlue) */
+  const float *input_proj_w, *input_proj_b; /* (d,input_dim),(d,) or NULL when input_dim == d == 256 (LGN:361-364); required by dim_lgl_create */
+  const float* posenc_Wr;             /* posenc.Wr.weight (d / heads / 2, 2) = (32,2), LighterGlue (48,2) */
   const float* confidence_thresholds; /* buffer (n_layers,) (LGN:581-584) */
   const dim_lg_layer_weights* layers; /* [n_layers] */
 } dim_lg_weights;
@@ -355,6 +356,11 @@ typedef struct dim_lg_config {
 typedef struct dim_lg dim_lg;
 
 int dim_lg_create(const dim_lg_weights* w, const dim_lg_config* cfg, int max_pairs, int max_kpts, dim_lg** out);
+/* LighterGlue: LightGlue at another shape (reference thirdparty/accelerated_features/modules/lighterglue.py:12-27: input_dim 64, descriptor_dim
+ * 96, ONE head of 96, 6 layers).  Accepts (descriptor_dim, num_heads) = (96, 1); (256, 4) is dim_lg_create; everything else fails with a
+ * dim_last_error text.  The result is an ordinary dim_lg: dim_lg_match / destroy / max_kpts / debug_desc (rows of descriptor_dim floats) and
+ * dim_handle_tune_set work on it unchanged.  A 96-wide handle runs in the split arithmetics only (dim_tune_set key 1 = 2 or 1, not 0). */
+int dim_lgl_create(const dim_lg_weights* w, const dim_lg_config* cfg, int descriptor_dim, int num_heads, int max_pairs, int max_kpts, dim_lg** out);
 void dim_lg_destroy(dim_lg* h);
 /* Row stride (>= max_kpts, multiple of 4) of the per-point output arrays below. */
 int dim_lg_max_kpts(dim_lg* h);
