@@ -101,7 +101,7 @@ class AlikeHIP(capi.ResidentHandle):
 
     def extract_batch_guarded(self, images: torch.Tensor, logger=None):
         """extract_batch under the fp16x3 range guard (capi.run_guarded): the convolutions and head products run as fp16 splits on the
-        matrix cores (alike.hip, gemm_x6.hip), exact for |activation| <= 4094; a call that leaves that range is repeated on the fp32
+        matrix cores (nhwc_conv.hip, gemm_x6.hip), exact for |activation| <= 4094; a call that leaves that range is repeated on the fp32
         paths.  Synchronises."""
         return self.guarded(lambda: self.extract_batch(images), "ALIKE", logger)
 

@@ -1,141 +1,11 @@
-// ALIKE (thirdparty/alike/{alnet,alike,soft_detect}.py) kernels for gfx950: the encoder / aggregation convolutions with eval-mode
-// BatchNorm folded in, the score map WITHOUT the descriptor map (single-head models: the score row of convhead2 is applied to the
-// three low-resolution groups before they are up-sampled), and the sparse descriptor head (convhead2 only at the four pixels around a
-// keypoint).  The dim-channel maps x1234 / descriptor_map (alnet.py:173-180) are never stored.
-// Arithmetic: fp16x3 on v_mfma_f32_32x32x16_f16 (SplitMma<2>, dim_common.h) by default, fp32 MFMA (v_mfma_f32_32x32x2_f32) otherwise.
+// ALIKE (thirdparty/alike/{alnet,alike,soft_detect}.py) kernels for gfx950: the score map WITHOUT the descriptor map (single-head models: the
+// score row of convhead2 is applied to the three low-resolution groups before they are up-sampled), and the sparse descriptor head (convhead2
+// only at the four pixels around a keypoint).  The dim-channel maps x1234 / descriptor_map (alnet.py:173-180) are never stored.
+// The encoder / aggregation convolutions are nhwc_conv.hip's kernel; the head products are the library's GEMMs.
 // Every reduction has a fixed order; no floating-point atomics.
 #include "alike_kernels.h"
 
 namespace {
-
-// ---------------------------------------------------------------------------
-// Convolution as an implicit GEMM without LDS.  One wave owns an 8 wide x 4 tall pixel tile (MFMA row i = pixel (i & 7, i >> 3)) and
-// all NT 32-channel column tiles; a workgroup is 2 x 2 waves = 16 x 8 pixels.
-// A operand (32x16 k-step): lane l supplies pixel i = l & 31, channels 16 c0 + 8 (l >> 5) + 0..7 of one tap: two 16-byte loads from
-// the NHWC map, split on the fly.  B operand: split_weights' fragment order puts lane l's 8 halves of (plane, column tile, k-step)
-// at 16-byte slot ((plane * NB + nt) * KS + ks) * 64 + l.
-// C layout (dim_common.h): lane l, register r = row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31 -> pixel x = (r & 3) + 4 (l >> 5),
-// y = r >> 2: the 16 registers of a lane are one 4 x 4 pixel block of one channel, so both max-pools (alnet.py:101-102) reduce in registers.
-template <int MODE, int NT>
-__global__ __launch_bounds__(256) void ak_conv_kernel(const AkConv a, const unsigned short* __restrict__ wsplit, const float* __restrict__ inv_ch) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.z;
-  const int x0 = blockIdx.x * 16 + (wave & 1) * 8, y0 = blockIdx.y * 8 + (wave >> 1) * 4;
-  const int i = lane & 31, kh = lane >> 5;
-  const int px = x0 + (i & 7), py = y0 + (i >> 3);
-  const int KS = (a.taps * a.cin_pad + a.cin2_pad) / 16;
-  f32x16 acc[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
-
-  auto step = [&](const float (&v)[8], int ks) {
-    if constexpr (MODE == 2) {
-      using P = SplitMma<2>;
-      u32x4 ap[2];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        unsigned p[2];
-        P::split(v[2 * e], v[2 * e + 1], P::act_scale(), p);
-        ap[0][e] = p[0]; ap[1][e] = p[1];
-      }
-      const u32x4* wf = (const u32x4*)wsplit;
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        const u32x4 bh = wf[((size_t)(0 * NT + nt) * KS + ks) * 64 + lane], bl = wf[((size_t)(1 * NT + nt) * KS + ks) * 64 + lane];
-        acc[nt] = P::mma(ap[1], bh, acc[nt]);   // smallest cross terms first: l*h, h*l, h*h
-        acc[nt] = P::mma(ap[0], bl, acc[nt]);
-        acc[nt] = P::mma(ap[0], bh, acc[nt]);
-      }
-    } else {
-      // fp32 MFMA (32x32x2): call j contracts the channel pair {j, 8 + j} of the step: lane half kh supplies its own v[j] (channel 8 kh + j) and
-      // the matching weight row, so no value changes lanes
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float* wrow = a.w32 + ((size_t)ks * 16 + 8 * kh + j) * a.n_pad + (lane & 31);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[nt] = mfma32(v[j], wrow[nt * 32], acc[nt]);
-      }
-    }
-  };
-
-  int ks = 0;
-  for (int tap = 0; tap < a.taps; ++tap) {
-    const int dy = a.taps == 9 ? tap / 3 - 1 : 0, dx = a.taps == 9 ? tap % 3 - 1 : 0;
-    const int yy = py + dy, xx = px + dx;
-    if (a.img3) {
-      const bool ok = yy >= 0 && yy < a.in_h && xx >= 0 && xx < a.in_w && kh == 0;
-      float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (ok) {
-        const float* p = a.in + (((size_t)b * a.in_h + yy) * a.in_w + xx) * 3;
-        v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
-      }
-      step(v, ks++);
-    } else {
-      const bool ok = yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
-      const float* p = a.in + (((size_t)b * a.H + (ok ? yy : 0)) * a.W + (ok ? xx : 0)) * a.cin_pad + 8 * kh;
-      for (int c0 = 0; c0 < a.cin_pad; c0 += 16) {
-        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (ok) {
-          const float4 u0 = *(const float4*)(p + c0), u1 = *(const float4*)(p + c0 + 4);
-          v[0] = u0.x; v[1] = u0.y; v[2] = u0.z; v[3] = u0.w; v[4] = u1.x; v[5] = u1.y; v[6] = u1.z; v[7] = u1.w;
-        }
-        step(v, ks++);
-      }
-    }
-  }
-  if (a.in2 != nullptr) {
-    const bool ok = py < a.H && px < a.W;
-    const float* p = a.in2 + (((size_t)b * a.H + (ok ? py : 0)) * a.W + (ok ? px : 0)) * a.cin2_pad + 8 * kh;
-    for (int c0 = 0; c0 < a.cin2_pad; c0 += 16) {
-      float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (ok) {
-        const float4 u0 = *(const float4*)(p + c0), u1 = *(const float4*)(p + c0 + 4);
-        v[0] = u0.x; v[1] = u0.y; v[2] = u0.z; v[3] = u0.w; v[4] = u1.x; v[5] = u1.y; v[6] = u1.z; v[7] = u1.w;
-      }
-      step(v, ks++);
-    }
-  }
-
-  // epilogue: exact inverse scale of the split, folded BatchNorm / downsample bias, ReLU, store (+ pooled copy)
-  float track = 0.f;
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int col = nt * 32 + (lane & 31);
-    const float inv = MODE == 2 ? inv_ch[col] : 1.0f, bias = a.bias[col];
-    const bool col_ok = col < a.out_c;
-    float val[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float v = acc[nt][r] * inv + bias;
-      if (a.relu) v = fmaxf(v, 0.f);
-      val[r] = v;
-      const int x = x0 + (r & 3) + 4 * kh, y = y0 + (r >> 2);
-      if (col_ok && x < a.W && y < a.H) {
-        a.out[(((size_t)b * a.H + y) * a.W + x) * a.out_c + col] = v;
-        track = fmaxf(track, fabsf(v));
-      }
-    }
-    if (a.pool == 4) {
-      float m = val[0];
-#pragma unroll
-      for (int r = 1; r < 16; ++r) m = fmaxf(m, val[r]);
-      const int x = x0 + 4 * kh;
-      if (col_ok && x < a.W && y0 < a.H) a.pooled[(((size_t)b * (a.H / 4) + y0 / 4) * (a.W / 4) + x / 4) * a.out_c + col] = m;
-    } else if (a.pool == 2) {
-#pragma unroll
-      for (int qy = 0; qy < 2; ++qy)
-#pragma unroll
-        for (int qx = 0; qx < 2; ++qx) {
-          const int r0 = (2 * qy) * 4 + 2 * qx;
-          const float m = fmaxf(fmaxf(val[r0], val[r0 + 1]), fmaxf(val[r0 + 4], val[r0 + 5]));
-          const int x = x0 + 4 * kh + 2 * qx, y = y0 + 2 * qy;
-          if (col_ok && x < a.W && y < a.H) a.pooled[(((size_t)b * (a.H / 2) + y / 2) * (a.W / 2) + x / 2) * a.out_c + col] = m;
-        }
-    }
-  }
-  if (MODE == 2) sat_report(a.sat, track);
-}
 
 // ---------------------------------------------------------------------------
 // bilinear up-sampling with align_corners=True (alnet.py:136-147) of channel `ch` of a low-resolution map [Hl][Wl][stride] at pixel (y, x)
@@ -274,32 +144,6 @@ __global__ __launch_bounds__(256) void ak_desc_blend_kernel(const float* __restr
 }
 
 }  // namespace
-
-int launch_ak_conv(const AkConv& a, bool x3, hipStream_t s) {
-  DIM_REQUIRE(a.in && a.out && a.bias && a.w32 && (!x3 || (a.wx && a.wx->dev && a.wx->mode == 2 && a.wx->n_pad == a.n_pad)), "ak_conv: null operand");
-  DIM_REQUIRE((a.taps == 9 || a.taps == 1) && a.cin_pad % 16 == 0 && a.cin2_pad % 16 == 0 && a.out_c % 16 == 0 && a.n_pad % 32 == 0 && a.n_pad >= 32 &&
-              a.n_pad <= 128 && a.out_c <= a.n_pad, "ak_conv: channels (cin %d, cin2 %d, out %d, n_pad %d)", a.cin_pad, a.cin2_pad, a.out_c, a.n_pad);
-  DIM_REQUIRE(!a.img3 || a.cin_pad == 16, "ak_conv: the image layer has one 16-channel k-step per tap");
-  DIM_REQUIRE(a.pool == 0 || ((a.pool == 2 || a.pool == 4) && a.pooled && a.H % a.pool == 0 && a.W % a.pool == 0), "ak_conv: pool %d on %dx%d", a.pool, a.H, a.W);
-  DIM_REQUIRE(a.batch >= 1 && a.H >= 1 && a.W >= 1, "ak_conv: empty map");
-  const dim3 grid(cdiv(a.W, 16), cdiv(a.H, 8), a.batch);
-  const unsigned short* wsplit = x3 ? a.wx->dev : nullptr;
-  const float* inv = x3 ? a.wx->inv_ch() : nullptr;
-#define AK_CONV(MODE, NT) hipLaunchKernelGGL(HIP_KERNEL_NAME(ak_conv_kernel<MODE, NT>), grid, dim3(256), 0, s, a, wsplit, inv)
-  switch ((x3 ? 10 : 0) + a.n_pad / 32) {
-    case 1: AK_CONV(0, 1); break;
-    case 2: AK_CONV(0, 2); break;
-    case 3: AK_CONV(0, 3); break;
-    case 4: AK_CONV(0, 4); break;
-    case 11: AK_CONV(2, 1); break;
-    case 12: AK_CONV(2, 2); break;
-    case 13: AK_CONV(2, 3); break;
-    default: AK_CONV(2, 4); break;
-  }
-#undef AK_CONV
-  DIM_LAUNCH_CHECK();
-  return 0;
-}
 
 int launch_ak_project(const float* f, int fq, int q, const float* ws, float* out, int n_pixels, hipStream_t s) {
   hipLaunchKernelGGL(ak_project_kernel, dim3(cdiv(n_pixels, 256)), dim3(256), 0, s, f, fq, q, ws, out, n_pixels);

@@ -10,14 +10,10 @@
 #include "../../include/dim_hip.h"
 #include "alike_kernels.h"
 #include "aliked_kernels.h"
+#include "nhwc_conv.h"
 #include "sp_kernels.h"
 
 namespace {
-// one convolution layer in kernel layout: the [K][N] operand split for the matrix cores and as fp32 [K][n_pad], bias [n_pad]
-struct AkLayer {
-  SplitWeights wx; float* w32 = nullptr; float* bias = nullptr;
-  int cin_pad = 16, cin2_pad = 0, taps = 9, n_pad = 32, out_c = 16;
-};
 constexpr int AK_BAND_PIXELS = 16384;   // alike-l's score map: pixels per row band of the convhead1 product (scratch independent of the image height)
 }  // namespace
 
@@ -25,7 +21,7 @@ struct dim_alike {
   DimHandleBase base;   // first member: dim_handle_tune_set
   dim_alike_config cfg;
   int max_batch, max_h, max_w, capacity, stride;
-  AkLayer L[8], A[3];   // the eight 3x3 convolutions (the ResBlock tails carry their downsample), conv2 / conv3 / conv4
+  NhwcConvLayer L[8], A[3];   // the eight 3x3 convolutions (the ResBlock tails carry their downsample: the BatchNorm scale is folded into the 3x3 rows only), conv2 / conv3 / conv4
   float *w1, *ws, *h1_w, *h2_w;   // conv1 [c1p][q]; score row of convhead2 [dim]; convhead1 / convhead2[0:dim] as [dim][dim] GEMM operands
   SplitWeights g_h1, g_h2;
   float *t1, *x1, *p2, *t2, *x2, *p3, *t3, *x3, *p4, *t4, *x4, *f2, *f3, *f4, *q2, *q3, *q4, *score, *nms;
@@ -37,29 +33,6 @@ struct dim_alike {
   unsigned long long* topk_keys;
   int last_hp, last_wp;
 };
-
-namespace {
-// OIHW conv weight (optionally scaled per output channel) into rows [row0 + tap * cin_pad + ci] of a [K][N] operand
-void put_rows(std::vector<float>& kn, int N, int row0, const float* w, int co, int ci, int k, int cin_pad, const std::vector<double>* scale) {
-  for (int a = 0; a < co; ++a)
-    for (int b = 0; b < ci; ++b)
-      for (int t = 0; t < k * k; ++t) {
-        const float v = w[((size_t)a * ci + b) * k * k + t];
-        kn[((size_t)row0 + (size_t)t * cin_pad + b) * N + a] = scale ? (float)((double)v * (*scale)[a]) : v;
-      }
-}
-int upload_layer(DimHandleBase* hb, AkLayer* L, const std::vector<float>& kn, int K, int N, const std::vector<float>& bias) {
-  L->n_pad = ak_pad32(N); L->out_c = ak_pad16(N);
-  DIM_TRY(dim_upload_gemm_split(hb, &L->wx, kn.data(), K, N, L->n_pad, 2));
-  std::vector<float> w32((size_t)K * L->n_pad, 0.0f), b(L->n_pad, 0.0f);
-  for (int k = 0; k < K; ++k)
-    for (int n = 0; n < N; ++n) w32[(size_t)k * L->n_pad + n] = kn[(size_t)k * N + n];
-  for (int n = 0; n < N; ++n) b[n] = bias[n];
-  DIM_TRY(dim_upload_f32(hb, &L->w32, w32));
-  DIM_TRY(dim_upload_f32(hb, &L->bias, b));
-  return 0;
-}
-}  // namespace
 
 extern "C" {
 
@@ -113,34 +86,34 @@ int dim_alike_create(const dim_alike_weights* w, const dim_alike_config* cfg, in
   for (int i = 0; i < 8; ++i) {
     const int blk = i / 2, co = cout_of[blk], ci = (i & 1) ? co : cin_of[blk];
     DIM_REQUIRE(cw[i], "dim_alike_create: 3x3 convolution %d is null", i);
-    AkLayer& L = h->L[i];
-    L.taps = 9; L.cin_pad = ak_pad16(ci);
-    L.cin2_pad = ((i & 1) && blk > 0) ? ak_pad16(cin_of[blk]) : 0;
+    NhwcConvLayer& L = h->L[i];
+    L.taps = 9; L.cin_pad = dim_pad16(ci);
+    L.cin2_pad = ((i & 1) && blk > 0) ? dim_pad16(cin_of[blk]) : 0;
     const int K = 9 * L.cin_pad + L.cin2_pad;
     std::vector<float> kn((size_t)K * co, 0.0f), bias(co);
-    put_rows(kn, co, 0, cw[i], co, ci, 3, L.cin_pad, &sc[i]);
+    nhwc_conv_pack_oihw(kn, co, 0, cw[i], co, ci, 3, L.cin_pad, &sc[i]);
     for (int c = 0; c < co; ++c) bias[c] = (float)bi[i][c];
     if (L.cin2_pad) {
       DIM_REQUIRE(dsw[blk] && dsb[blk], "dim_alike_create: block%d.downsample is null", blk + 1);
-      put_rows(kn, co, 9 * L.cin_pad, dsw[blk], co, cin_of[blk], 1, L.cin2_pad, nullptr);
+      nhwc_conv_pack_oihw(kn, co, 9 * L.cin_pad, dsw[blk], co, cin_of[blk], 1, L.cin2_pad, nullptr);
       for (int c = 0; c < co; ++c) bias[c] = (float)(bi[i][c] + (double)dsb[blk][c]);
     }
-    DIM_TRY(upload_layer(hb, &L, kn, K, co, bias));
+    DIM_TRY(nhwc_conv_upload(hb, &L, kn, K, co, bias));
   }
   {  // aggregation: conv2 / conv3 / conv4 (1x1, bias-free, ReLU; AKN:167-169) as layers; conv1 (AKN:166) is evaluated per pixel by the head kernels
     const float* aw[3] = {w->conv2, w->conv3, w->conv4};
     const int aci[3] = {c2, c3, c4};
     for (int g = 0; g < 3; ++g) {
       DIM_REQUIRE(aw[g], "dim_alike_create: conv%d is null", g + 2);
-      AkLayer& L = h->A[g];
-      L.taps = 1; L.cin_pad = ak_pad16(aci[g]); L.cin2_pad = 0;
+      NhwcConvLayer& L = h->A[g];
+      L.taps = 1; L.cin_pad = dim_pad16(aci[g]); L.cin2_pad = 0;
       std::vector<float> kn((size_t)L.cin_pad * q, 0.0f), bias(q, 0.0f);
-      put_rows(kn, q, 0, aw[g], q, aci[g], 1, L.cin_pad, nullptr);
-      DIM_TRY(upload_layer(hb, &L, kn, L.cin_pad, q, bias));
+      nhwc_conv_pack_oihw(kn, q, 0, aw[g], q, aci[g], 1, L.cin_pad, nullptr);
+      DIM_TRY(nhwc_conv_upload(hb, &L, kn, L.cin_pad, q, bias));
     }
     DIM_REQUIRE(w->conv1, "dim_alike_create: conv1 is null");
-    std::vector<float> w1((size_t)ak_pad16(c1) * q, 0.0f);
-    put_rows(w1, q, 0, w->conv1, q, c1, 1, ak_pad16(c1), nullptr);
+    std::vector<float> w1((size_t)dim_pad16(c1) * q, 0.0f);
+    nhwc_conv_pack_oihw(w1, q, 0, w->conv1, q, c1, 1, dim_pad16(c1), nullptr);
     DIM_TRY(dim_upload_f32(hb, &h->w1, w1));
   }
   {  // heads (AKN:176-181): [K = dim][N = dim] operands; the score row of convhead2 on its own
@@ -159,7 +132,7 @@ int dim_alike_create(const dim_alike_weights* w, const dim_alike_config* cfg, in
     }
   }
   const size_t B = max_batch, Hp = ((size_t)max_h + 31) / 32 * 32, Wp = ((size_t)max_w + 31) / 32 * 32, NP = Hp * Wp, cap = capacity;
-  const size_t p1 = ak_pad16(c1), p2 = ak_pad16(c2), p3 = ak_pad16(c3), p4 = ak_pad16(c4), fq = ak_pad16(q);
+  const size_t p1 = dim_pad16(c1), p2 = dim_pad16(c2), p3 = dim_pad16(c3), p4 = dim_pad16(c4), fq = dim_pad16(q);
   DIM_TRY(dim_dev_alloc(hb, &h->t1, B * NP * p1)); DIM_TRY(dim_dev_alloc(hb, &h->x1, B * NP * p1)); DIM_TRY(dim_dev_alloc(hb, &h->p2, B * NP / 4 * p1));
   DIM_TRY(dim_dev_alloc(hb, &h->t2, B * NP / 4 * p2)); DIM_TRY(dim_dev_alloc(hb, &h->x2, B * NP / 4 * p2)); DIM_TRY(dim_dev_alloc(hb, &h->p3, B * NP / 64 * p2));
   DIM_TRY(dim_dev_alloc(hb, &h->t3, B * NP / 64 * p3)); DIM_TRY(dim_dev_alloc(hb, &h->x3, B * NP / 64 * p3)); DIM_TRY(dim_dev_alloc(hb, &h->p4, B * NP / 1024 * p3));
@@ -192,30 +165,29 @@ int dim_alike_extract(dim_alike* h, const float* images_dev, int batch, int H, i
   const int H2 = Hp / 2, W2 = Wp / 2, H8 = Hp / 8, W8 = Wp / 8, H32 = Hp / 32, W32 = Wp / 32;
   const bool x3 = dim_precision_mode() == 2;   // fp16x3 on the matrix cores; every other mode runs the fp32 MFMA forms
   unsigned* const sat = dim_sat_counter(DIM_SAT_ALIKE);
-#define AK_RUN(x) do { int rc__ = (x); if (rc__ != 0) return rc__; } while (0)
-  auto conv = [&](const AkLayer& L, const float* in, const float* in2, float* out, float* pooled, int pool, int Hh, int Ww, bool img) -> int {
-    AkConv a;
+  auto conv = [&](const NhwcConvLayer& L, const float* in, const float* in2, float* out, float* pooled, int pool, int Hh, int Ww, bool img) -> int {
+    NhwcConv a;
     a.in = in; a.cin_pad = L.cin_pad; a.taps = L.taps; a.in2 = in2; a.cin2_pad = in2 ? L.cin2_pad : 0;
-    a.img3 = img ? 1 : 0; a.in_h = H; a.in_w = W;
+    a.img3 = img ? 1 : 0; a.in_h = img ? H : Hh; a.in_w = img ? W : Ww;   // the image layer reads the unpadded image into the padded frame
     a.wx = &L.wx; a.w32 = L.w32; a.bias = L.bias; a.n_pad = L.n_pad; a.out = out; a.out_c = L.out_c; a.pooled = pooled; a.pool = pool;
     a.relu = 1; a.batch = batch; a.H = Hh; a.W = Ww; a.sat = sat;
-    return launch_ak_conv(a, x3, s);
+    return launch_nhwc_conv(a, x3, s);
   };
   // encoder (AKN:157-163): block1 on the padded frame, max-pools fused into the epilogues that feed them
-  AK_RUN(conv(h->L[0], images_dev, nullptr, h->t1, nullptr, 0, Hp, Wp, true));
-  AK_RUN(conv(h->L[1], h->t1, nullptr, h->x1, h->p2, 2, Hp, Wp, false));
-  AK_RUN(conv(h->L[2], h->p2, nullptr, h->t2, nullptr, 0, H2, W2, false));
-  AK_RUN(conv(h->L[3], h->t2, h->p2, h->x2, h->p3, 4, H2, W2, false));
-  AK_RUN(conv(h->L[4], h->p3, nullptr, h->t3, nullptr, 0, H8, W8, false));
-  AK_RUN(conv(h->L[5], h->t3, h->p3, h->x3, h->p4, 4, H8, W8, false));
-  AK_RUN(conv(h->L[6], h->p4, nullptr, h->t4, nullptr, 0, H32, W32, false));
-  AK_RUN(conv(h->L[7], h->t4, h->p4, h->x4, nullptr, 0, H32, W32, false));
+  DIM_RUN(conv(h->L[0], images_dev, nullptr, h->t1, nullptr, 0, Hp, Wp, true));
+  DIM_RUN(conv(h->L[1], h->t1, nullptr, h->x1, h->p2, 2, Hp, Wp, false));
+  DIM_RUN(conv(h->L[2], h->p2, nullptr, h->t2, nullptr, 0, H2, W2, false));
+  DIM_RUN(conv(h->L[3], h->t2, h->p2, h->x2, h->p3, 4, H2, W2, false));
+  DIM_RUN(conv(h->L[4], h->p3, nullptr, h->t3, nullptr, 0, H8, W8, false));
+  DIM_RUN(conv(h->L[5], h->t3, h->p3, h->x3, h->p4, 4, H8, W8, false));
+  DIM_RUN(conv(h->L[6], h->p4, nullptr, h->t4, nullptr, 0, H32, W32, false));
+  DIM_RUN(conv(h->L[7], h->t4, h->p4, h->x4, nullptr, 0, H32, W32, false));
   // aggregation at the levels' own resolutions (AKN:167-169)
-  AK_RUN(conv(h->A[0], h->x2, nullptr, h->f2, nullptr, 0, H2, W2, false));
-  AK_RUN(conv(h->A[1], h->x3, nullptr, h->f3, nullptr, 0, H8, W8, false));
-  AK_RUN(conv(h->A[2], h->x4, nullptr, h->f4, nullptr, 0, H32, W32, false));
+  DIM_RUN(conv(h->A[0], h->x2, nullptr, h->f2, nullptr, 0, H2, W2, false));
+  DIM_RUN(conv(h->A[1], h->x3, nullptr, h->f3, nullptr, 0, H8, W8, false));
+  DIM_RUN(conv(h->A[2], h->x4, nullptr, h->f4, nullptr, 0, H32, W32, false));
   const int fq = h->A[0].out_c;
-  const AkFeat F{h->x1, h->f2, h->f3, h->f4, h->w1, Hp, Wp, ak_pad16(c1), q, fq};
+  const AkFeat F{h->x1, h->f2, h->f3, h->f4, h->w1, Hp, Wp, dim_pad16(c1), q, fq};
   auto head_gemm = [&](const float* Ain, const float* w32, const SplitWeights& wx, float* Cout, int M, const int* rows, int relu) -> int {
     GemmArgs g;
     g.A0 = Ain; g.lda0 = dim; g.strideA0 = (long long)h->rows_cap * dim; g.B = w32; g.ldb = dim;
@@ -227,51 +199,50 @@ int dim_alike_extract(dim_alike* h, const float* images_dev, int batch, int H, i
   if (h->cfg.single_head) {
     // score = sigmoid(w_s . x1234) with the three up-sampled groups projected to ONE channel before the interpolation (exact in real
     // arithmetic: the interpolation is linear and convhead2 follows it without an activation, AKN:170-181)
-    AK_RUN(launch_ak_project(h->f2, fq, q, h->ws + q, h->q2, batch * H2 * W2, s));
-    AK_RUN(launch_ak_project(h->f3, fq, q, h->ws + 2 * q, h->q3, batch * H8 * W8, s));
-    AK_RUN(launch_ak_project(h->f4, fq, q, h->ws + 3 * q, h->q4, batch * H32 * W32, s));
-    AK_RUN(launch_ak_score(F, h->ws, h->q2, h->q3, h->q4, h->score, batch, H, W, s));
+    DIM_RUN(launch_ak_project(h->f2, fq, q, h->ws + q, h->q2, batch * H2 * W2, s));
+    DIM_RUN(launch_ak_project(h->f3, fq, q, h->ws + 2 * q, h->q3, batch * H8 * W8, s));
+    DIM_RUN(launch_ak_project(h->f4, fq, q, h->ws + 3 * q, h->q4, batch * H32 * W32, s));
+    DIM_RUN(launch_ak_score(F, h->ws, h->q2, h->q3, h->q4, h->score, batch, H, W, s));
   } else {
     // alike-l: relu(convhead1 . x1234) is dense work (AKN:176-177): x1234 is assembled per row band, the 128 x 128 product runs on the
     // matrix cores and the band is contracted with w_s; the band scratch does not depend on the image height
     const int band = AK_BAND_PIXELS / W > 0 ? AK_BAND_PIXELS / W : 1;
     for (int y0 = 0; y0 < H; y0 += band) {
       const int rows = (y0 + band <= H ? band : H - y0) * W;
-      AK_RUN(launch_ak_rows(F, nullptr, nullptr, 0, y0, rows, h->X, dim, (long long)h->rows_cap * dim, batch, H, W, sat, s));
-      AK_RUN(head_gemm(h->X, h->h1_w, h->g_h1, h->Y, rows, nullptr, 1));
-      AK_RUN(launch_ak_contract(h->Y, dim, (long long)h->rows_cap * dim, h->ws, dim, h->score, y0, rows, batch, H, W, s));
+      DIM_RUN(launch_ak_rows(F, nullptr, nullptr, 0, y0, rows, h->X, dim, (long long)h->rows_cap * dim, batch, H, W, sat, s));
+      DIM_RUN(head_gemm(h->X, h->h1_w, h->g_h1, h->Y, rows, nullptr, 1));
+      DIM_RUN(launch_ak_contract(h->Y, dim, (long long)h->rows_cap * dim, h->ws, dim, h->score, y0, rows, batch, H, W, s));
     }
   }
   // DKD (AKD:98-134): NMS radius 2 (hard-coded, AKD:102), asymmetric border, top-k or threshold selection
-  AK_RUN(launch_nms(h->score, h->nms, batch, H, W, 2, s));
-  AK_RUN(launch_ak_border(h->nms, batch, H, W, s));
+  DIM_RUN(launch_nms(h->score, h->nms, batch, H, W, 2, s));
+  DIM_RUN(launch_ak_border(h->nms, batch, H, W, s));
   if (h->cfg.top_k > 0) {
     // torch.topk over the border-cleared NMS map (AKD:111-113): every positive maximum is a candidate, sorted; zero-valued pixels fill up
-    AK_RUN(launch_select_ex(h->nms, batch, H, W, 0.f, nullptr, 0, h->rowcount, h->rowoff, h->ncand, h->cand_score, h->cand_idx, 0, s));
-    AK_RUN(launch_topk(h->cand_score, h->cand_idx, h->ncand, batch, H, W, h->cfg.top_k, cap, h->kpts_px, h->sc_tmp, n_kpts_dev, h->topk_keys, 1, s));
-    AK_RUN(launch_topk_zero_fill(h->nms, batch, H, W, 0.f, 0, h->cfg.top_k, cap, h->kpts_px, h->sc_tmp, n_kpts_dev, s));
+    DIM_RUN(launch_select_ex(h->nms, batch, H, W, 0.f, nullptr, 0, h->rowcount, h->rowoff, h->ncand, h->cand_score, h->cand_idx, 0, s));
+    DIM_RUN(launch_topk(h->cand_score, h->cand_idx, h->ncand, batch, H, W, h->cfg.top_k, cap, h->kpts_px, h->sc_tmp, n_kpts_dev, h->topk_keys, 1, s));
+    DIM_RUN(launch_topk_zero_fill(h->nms, batch, H, W, 0.f, 0, h->cfg.top_k, cap, h->kpts_px, h->sc_tmp, n_kpts_dev, s));
   } else {
-    AK_RUN(launch_al_mean(h->score, batch, H * W, h->partial, h->mean, s));
+    DIM_RUN(launch_al_mean(h->score, batch, H * W, h->partial, h->mean, s));
     const float thr = (float)h->cfg.scores_th;
-    if (thr > 0.f) AK_RUN(launch_select_ex(h->nms, batch, H, W, thr, nullptr, 0, h->rowcount, h->rowoff, h->ncand, h->cand_score, h->cand_idx, 1, s));
-    AK_RUN(launch_al_pick_threshold(h->ncand, h->mean, thr, h->thr_eff, batch, s));   // the mean when scores_th <= 0 or nothing passes (AKD:115-122), per image
-    AK_RUN(launch_select_ex(h->nms, batch, H, W, 0.f, h->thr_eff, 0, h->rowcount, h->rowoff, h->ncand, h->cand_score, h->cand_idx, 0, s));
-    AK_RUN(launch_topk(h->cand_score, h->cand_idx, h->ncand, batch, H, W, h->cfg.n_limit, cap, h->kpts_px, h->sc_tmp, n_kpts_dev, h->topk_keys, 0, s));
+    if (thr > 0.f) DIM_RUN(launch_select_ex(h->nms, batch, H, W, thr, nullptr, 0, h->rowcount, h->rowoff, h->ncand, h->cand_score, h->cand_idx, 1, s));
+    DIM_RUN(launch_al_pick_threshold(h->ncand, h->mean, thr, h->thr_eff, batch, s));   // the mean when scores_th <= 0 or nothing passes (AKD:115-122), per image
+    DIM_RUN(launch_select_ex(h->nms, batch, H, W, 0.f, h->thr_eff, 0, h->rowcount, h->rowoff, h->ncand, h->cand_score, h->cand_idx, 0, s));
+    DIM_RUN(launch_topk(h->cand_score, h->cand_idx, h->ncand, batch, H, W, h->cfg.n_limit, cap, h->kpts_px, h->sc_tmp, n_kpts_dev, h->topk_keys, 0, s));
   }
   // soft-argmax refinement over the 5x5 window, temperature 0.1 (AKD:139-178); its bilinear score sample is ALIKE's `scores` (AKD:180-187)
-  AK_RUN(launch_al_dkd_refine(h->score, h->kpts_px, n_kpts_dev, h->kpts_norm, h->disp, scores_dev, kpts_xy_dev, batch, H, W, cap, 2, s));
+  DIM_RUN(launch_al_dkd_refine(h->score, h->kpts_px, n_kpts_dev, h->kpts_norm, h->disp, scores_dev, kpts_xy_dev, batch, H, W, cap, 2, s));
   // sparse descriptor head: x1234 at the four pixels around every keypoint, convhead (1 +) 2 on those rows only
-  AK_RUN(launch_ak_rows(F, h->kpts_norm, n_kpts_dev, cap, 0, 0, h->X, dim, (long long)h->rows_cap * dim, batch, H, W, sat, s));
+  DIM_RUN(launch_ak_rows(F, h->kpts_norm, n_kpts_dev, cap, 0, 0, h->X, dim, (long long)h->rows_cap * dim, batch, H, W, sat, s));
   const float* D = h->Y;
   if (h->cfg.single_head) {
-    AK_RUN(head_gemm(h->X, h->h2_w, h->g_h2, h->Y, 4 * cap, n_kpts_dev, 0));
+    DIM_RUN(head_gemm(h->X, h->h2_w, h->g_h2, h->Y, 4 * cap, n_kpts_dev, 0));
   } else {
-    AK_RUN(head_gemm(h->X, h->h1_w, h->g_h1, h->Y, 4 * cap, n_kpts_dev, 1));
-    AK_RUN(head_gemm(h->Y, h->h2_w, h->g_h2, h->X, 4 * cap, n_kpts_dev, 0));
+    DIM_RUN(head_gemm(h->X, h->h1_w, h->g_h1, h->Y, 4 * cap, n_kpts_dev, 1));
+    DIM_RUN(head_gemm(h->Y, h->h2_w, h->g_h2, h->X, 4 * cap, n_kpts_dev, 0));
     D = h->X;
   }
-  AK_RUN(launch_ak_desc_blend(D, dim, (long long)h->rows_cap * dim, h->kpts_norm, n_kpts_dev, desc_dev, dim, h->stride, cap, batch, H, W, s));
-#undef AK_RUN
+  DIM_RUN(launch_ak_desc_blend(D, dim, (long long)h->rows_cap * dim, h->kpts_norm, n_kpts_dev, desc_dev, dim, h->stride, cap, batch, H, W, s));
   h->last_hp = Hp; h->last_wp = Wp;
   return 0;
 }

@@ -1,32 +1,7 @@
 // Launchers of the ALIKE kernels (alike.hip).  All tensors NHWC fp32; reference lines are thirdparty/alike/{alnet,alike,soft_detect}.py.
+// The encoder / aggregation convolutions (alnet.py:27-30, 68-84, 166-169) are launch_nhwc_conv (nhwc_conv.h).
 #pragma once
 #include "dim_kernels.h"
-
-inline int ak_pad16(int c) { return (c + 15) / 16 * 16; }
-inline int ak_pad32(int c) { return (c + 31) / 32 * 32; }
-
-// One encoder / aggregation convolution with eval-mode BatchNorm folded in (alnet.py:27-30, 68-84, 166-169):
-//   out[b][y][x][co] = act( sum_{tap,ci} in[b][y+dy][x+dx][ci] w[tap*cin_pad+ci][co] + sum_ci in2[b][y][x][ci] w[taps*cin_pad+ci][co] + bias[co] )
-// zero padding; taps = 9 (3x3) or 1.  in2 (optional) is the ResBlock's identity input: its 1x1 `downsample` rides in the same
-// product as extra K rows, the BatchNorm scale is folded into the 3x3 rows, bias = BatchNorm bias + downsample bias.
-// img3: `in` is the unpadded [b][in_h][in_w][3] image; everything at or past in_h / in_w reads as the zero padding of alike.py:105-113.
-// pool = 2 | 4: the max-pooled copy of the activated map goes to `pooled` as well ([b][H/pool][W/pool][out_c]; H, W multiples of pool).
-// Channel strides: cin_pad / cin2_pad / out_c are multiples of 16 (padding channels hold zeros); the weights' n_pad is a multiple of 32.
-struct AkConv {
-  const float* in = nullptr; int cin_pad = 16; int taps = 9;
-  const float* in2 = nullptr; int cin2_pad = 0;
-  int img3 = 0, in_h = 0, in_w = 0;
-  const SplitWeights* wx = nullptr;   // fp16x3: split_weights(K, N, n_pad, 2) of the [K][N] operand
-  const float* w32 = nullptr;         // fp32: the same operand [K][n_pad]
-  const float* bias = nullptr;        // [n_pad]
-  int n_pad = 32;
-  float* out = nullptr; int out_c = 16;
-  float* pooled = nullptr; int pool = 0;
-  int relu = 1;
-  int batch = 1, H = 0, W = 0;
-  unsigned* sat = nullptr;            // fp16x3 range guard of the stored activations
-};
-int launch_ak_conv(const AkConv& a, bool x3, hipStream_t s);
 
 // sources of the never materialised dim-channel map x1234 (alnet.py:166-173) on the padded frame Hp x Wp: x1 ([..][c1p]) with conv1
 // (w1 [c1p][q], bias-free, ReLU) evaluated per pixel, f2 / f3 / f4 = relu(conv_g x_g) ([..][fq] at 1/2, 1/8, 1/32) interpolated with align_corners=True

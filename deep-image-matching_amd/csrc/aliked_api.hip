@@ -197,7 +197,6 @@ int dim_aliked_extract(dim_aliked* h, const float* images_dev, int batch, int H,
   const int pad_t = ph / 2, pad_l = pw / 2, Hp = H + ph, Wp = W + pw;
   const int H2 = Hp / 2, W2 = Wp / 2, H8 = Hp / 8, W8 = Wp / 8, H32 = Hp / 32, W32 = Wp / 32;
   const int NP = Hp * Wp, r = h->cfg.nms_radius, cap = h->capacity;
-#define AL_RUN(x) do { int rc__ = (x); if (rc__ != 0) return rc__; } while (0)
   // 1x1 convolutions on NHWC maps are plain GEMMs over pixels (weights already [cin][cout])
   // GEMMs: fp16x3 on the matrix cores (gemm_x6.hip) under the default arithmetic, plain fp32 MFMA otherwise
   const bool x3 = dim_precision_mode() == 2;
@@ -219,7 +218,7 @@ int dim_aliked_extract(dim_aliked* h, const float* images_dev, int batch, int H,
     if (rc) return rc;
     return launch_al_bn_apply(x, h->bn_alpha, h->bn_beta, res, dst, batch, npx, C, s);
   };
-  AL_RUN(launch_al_pad_replicate(images_dev, h->P, batch, H, W, Hp, Wp, pad_t, pad_l, in_channels, s));
+  DIM_RUN(launch_al_pad_replicate(images_dev, h->P, batch, H, W, Hp, Wp, pad_t, pad_l, in_channels, s));
   // Full- and half-resolution convolutions: fp16x3 on the matrix cores with the BatchNorm statistics reduced in the conv
   // epilogue (aliked_x3.hip) under the default arithmetic; the fp32 VALU kernels + a separate statistics pass otherwise
   // (dim_tune_set(1, 0 | 1): A/B checks and the range-guard fallback; aliked-t16).
@@ -255,26 +254,26 @@ int dim_aliked_extract(dim_aliked* h, const float* images_dev, int batch, int H,
     return launch_al_bn_apply_pool(x, a, bt, res, dst, pooled, batch, Hh, Ww, C, k, s);
   };
   // block1 (ConvBlock, ALN:367-393)
-  AL_RUN(conv_bn(h->P, 3, 16, 9, h->x_b1c1, h->b1c1, h->raw, c1, Hp, Wp, 0, 0, -1));
+  DIM_RUN(conv_bn(h->P, 3, 16, 9, h->x_b1c1, h->b1c1, h->raw, c1, Hp, Wp, 0, 0, -1));
   if (fuse_bn) {
-    AL_RUN(conv_bn(h->raw, c1, c1, 9, h->x_b1c2, h->b1c2, h->act, c1, Hp, Wp, 1, 1, 0));   // bn1 + SELU of conv1 in the staging; raw output -> act
-    AL_RUN(apply_pool(h->act, 1, nullptr, h->x1, h->p2, Hp, Wp, c1, 2));
+    DIM_RUN(conv_bn(h->raw, c1, c1, 9, h->x_b1c2, h->b1c2, h->act, c1, Hp, Wp, 1, 1, 0));   // bn1 + SELU of conv1 in the staging; raw output -> act
+    DIM_RUN(apply_pool(h->act, 1, nullptr, h->x1, h->p2, Hp, Wp, c1, 2));
   } else {
-    AL_RUN(apply(h->raw, 0, nullptr, h->act, NP, c1));
-    AL_RUN(conv_bn(h->act, c1, c1, 9, h->x_b1c2, h->b1c2, h->raw, c1, Hp, Wp, 1, 1, -1));
-    AL_RUN(apply_pool(h->raw, 1, nullptr, h->x1, h->p2, Hp, Wp, c1, 2));
+    DIM_RUN(apply(h->raw, 0, nullptr, h->act, NP, c1));
+    DIM_RUN(conv_bn(h->act, c1, c1, 9, h->x_b1c2, h->b1c2, h->raw, c1, Hp, Wp, 1, 1, -1));
+    DIM_RUN(apply_pool(h->raw, 1, nullptr, h->x1, h->p2, Hp, Wp, c1, 2));
   }
   // block2 (ResBlock, plain convs); its input p2 = avgpool2(x1) was written by apply_pool
-  AL_RUN(conv_bn(h->p2, c1, c1, 9, h->x_b2c1, h->b2c1, h->raw, c2, H2, W2, 2, 0, -1));
-  if (x3c) AL_RUN(launch_al_convx3(h->p2, c1, c1, 1, h->x_b2ds, h->b2ds_b, h->idn, c2, batch, H2, W2, nullptr, nullptr, nullptr, nullptr, s));
-  else AL_RUN(launch_al_conv1x1(h->p2, c1, h->b2ds_w, h->b2ds_b, h->idn, c2, batch * H2 * W2, AL_ACT_NONE, s));  // K = 16 / 8: below the GEMM's K granule
+  DIM_RUN(conv_bn(h->p2, c1, c1, 9, h->x_b2c1, h->b2c1, h->raw, c2, H2, W2, 2, 0, -1));
+  if (x3c) DIM_RUN(launch_al_convx3(h->p2, c1, c1, 1, h->x_b2ds, h->b2ds_b, h->idn, c2, batch, H2, W2, nullptr, nullptr, nullptr, nullptr, s));
+  else DIM_RUN(launch_al_conv1x1(h->p2, c1, h->b2ds_w, h->b2ds_b, h->idn, c2, batch * H2 * W2, AL_ACT_NONE, s));  // K = 16 / 8: below the GEMM's K granule
   if (fuse_bn) {
-    AL_RUN(conv_bn(h->raw, c2, c2, 9, h->x_b2c2, h->b2c2, h->act, c2, H2, W2, 3, 1, 0));
-    AL_RUN(apply_pool(h->act, 1, h->idn, h->x2, h->p3, H2, W2, c2, 4));
+    DIM_RUN(conv_bn(h->raw, c2, c2, 9, h->x_b2c2, h->b2c2, h->act, c2, H2, W2, 3, 1, 0));
+    DIM_RUN(apply_pool(h->act, 1, h->idn, h->x2, h->p3, H2, W2, c2, 4));
   } else {
-    AL_RUN(apply(h->raw, 0, nullptr, h->act, H2 * W2, c2));
-    AL_RUN(conv_bn(h->act, c2, c2, 9, h->x_b2c2, h->b2c2, h->raw, c2, H2, W2, 3, 1, -1));
-    AL_RUN(apply_pool(h->raw, 1, h->idn, h->x2, h->p3, H2, W2, c2, 4));
+    DIM_RUN(apply(h->raw, 0, nullptr, h->act, H2 * W2, c2));
+    DIM_RUN(conv_bn(h->act, c2, c2, 9, h->x_b2c2, h->b2c2, h->raw, c2, H2, W2, 3, 1, -1));
+    DIM_RUN(apply_pool(h->raw, 1, h->idn, h->x2, h->p3, H2, W2, c2, 4));
   }
   // block3 / block4 (ResBlock with DeformableConv2d, ALN:274-330)
   auto dcn_block = [&](const float* x, int Hh, int Ww, int ci, int co, const float* o1w, const float* o1b, const float* r1,
@@ -292,78 +291,77 @@ int dim_aliked_extract(dim_aliked* h, const float* images_dev, int batch, int H,
     if ((rc = conv1x1(x, ci, dsw, xds, dsb, h->idn, co, batch * Hh * Ww, AL_ACT_NONE))) return rc;
     return bn(h->raw, Hh * Ww, co, bni + 1, h->idn, dst);
   };
-  AL_RUN(dcn_block(h->p3, H8, W8, c2, c3, h->b3o1_w, h->b3o1_b, h->b3r1, h->b3o2_w, h->b3o2_b, h->b3r2, h->b3ds_w, h->b3ds_b, 4, h->x3, h->g_b3r1, h->g_b3r2, h->g_b3ds));
-  AL_RUN(launch_al_avgpool(h->x3, h->p4, batch, H8, W8, c3, 4, s));
-  AL_RUN(dcn_block(h->p4, H32, W32, c3, c4, h->b4o1_w, h->b4o1_b, h->b4r1, h->b4o2_w, h->b4o2_b, h->b4r2, h->b4ds_w, h->b4ds_b, 6, h->x4, h->g_b4r1, h->g_b4r2, h->g_b4ds));
+  DIM_RUN(dcn_block(h->p3, H8, W8, c2, c3, h->b3o1_w, h->b3o1_b, h->b3r1, h->b3o2_w, h->b3o2_b, h->b3r2, h->b3ds_w, h->b3ds_b, 4, h->x3, h->g_b3r1, h->g_b3r2, h->g_b3ds));
+  DIM_RUN(launch_al_avgpool(h->x3, h->p4, batch, H8, W8, c3, 4, s));
+  DIM_RUN(dcn_block(h->p4, H32, W32, c3, c4, h->b4o1_w, h->b4o1_b, h->b4r1, h->b4o2_w, h->b4o2_b, h->b4r2, h->b4ds_w, h->b4ds_b, 6, h->x4, h->g_b4r1, h->g_b4r2, h->g_b4ds));
   // feature aggregation + score head (ALN:656-669)
   if (tiny) {
-    AL_RUN(launch_al_conv1x1(h->x2, c2, h->hc2, nullptr, h->f2, G, batch * H2 * W2, AL_ACT_SELU, s));
-    AL_RUN(launch_al_conv1x1(h->x3, c3, h->hc3, nullptr, h->f3, G, batch * H8 * W8, AL_ACT_SELU, s));
-    AL_RUN(launch_al_conv1x1(h->x4, c4, h->hc4, nullptr, h->f4, G, batch * H32 * W32, AL_ACT_SELU, s));
+    DIM_RUN(launch_al_conv1x1(h->x2, c2, h->hc2, nullptr, h->f2, G, batch * H2 * W2, AL_ACT_SELU, s));
+    DIM_RUN(launch_al_conv1x1(h->x3, c3, h->hc3, nullptr, h->f3, G, batch * H8 * W8, AL_ACT_SELU, s));
+    DIM_RUN(launch_al_conv1x1(h->x4, c4, h->hc4, nullptr, h->f4, G, batch * H32 * W32, AL_ACT_SELU, s));
   } else {
-    AL_RUN(conv1x1(h->x2, 32, h->hc2, h->g_hc2, nullptr, h->f2, 32, batch * H2 * W2, AL_ACT_SELU));
-    AL_RUN(conv1x1(h->x3, 64, h->hc3, h->g_hc3, nullptr, h->f3, 32, batch * H8 * W8, AL_ACT_SELU));
-    AL_RUN(conv1x1(h->x4, 128, h->hc4, h->g_hc4, nullptr, h->f4, 32, batch * H32 * W32, AL_ACT_SELU));
+    DIM_RUN(conv1x1(h->x2, 32, h->hc2, h->g_hc2, nullptr, h->f2, 32, batch * H2 * W2, AL_ACT_SELU));
+    DIM_RUN(conv1x1(h->x3, 64, h->hc3, h->g_hc3, nullptr, h->f3, 32, batch * H8 * W8, AL_ACT_SELU));
+    DIM_RUN(conv1x1(h->x4, 128, h->hc4, h->g_hc4, nullptr, h->f4, 32, batch * H32 * W32, AL_ACT_SELU));
   }
   // s8 only; x1234 stays virtual.  The G -> 8 projections of the three up-sampled groups run at the maps' own resolutions
-  AL_RUN(launch_al_conv1x1(h->f2, G, h->sh0 + G * 8, nullptr, h->q2, 8, batch * H2 * W2, AL_ACT_NONE, s));
-  AL_RUN(launch_al_conv1x1(h->f3, G, h->sh0 + 2 * G * 8, nullptr, h->q3, 8, batch * H8 * W8, AL_ACT_NONE, s));
-  AL_RUN(launch_al_conv1x1(h->f4, G, h->sh0 + 3 * G * 8, nullptr, h->q4, 8, batch * H32 * W32, AL_ACT_NONE, s));
-  if (x3c) AL_RUN(launch_al_assemble_x3(h->x1, h->q2, h->q3, h->q4, h->asm_frag, h->asm_inv1, h->asm_inv0, h->s8, batch, Hp, Wp, s));
-  else AL_RUN(launch_al_assemble_proj(h->x1, h->q2, h->q3, h->q4, h->hc1, h->sh0, h->s8, c1, batch, Hp, Wp, s));
+  DIM_RUN(launch_al_conv1x1(h->f2, G, h->sh0 + G * 8, nullptr, h->q2, 8, batch * H2 * W2, AL_ACT_NONE, s));
+  DIM_RUN(launch_al_conv1x1(h->f3, G, h->sh0 + 2 * G * 8, nullptr, h->q3, 8, batch * H8 * W8, AL_ACT_NONE, s));
+  DIM_RUN(launch_al_conv1x1(h->f4, G, h->sh0 + 3 * G * 8, nullptr, h->q4, 8, batch * H32 * W32, AL_ACT_NONE, s));
+  if (x3c) DIM_RUN(launch_al_assemble_x3(h->x1, h->q2, h->q3, h->q4, h->asm_frag, h->asm_inv1, h->asm_inv0, h->s8, batch, Hp, Wp, s));
+  else DIM_RUN(launch_al_assemble_proj(h->x1, h->q2, h->q3, h->q4, h->hc1, h->sh0, h->s8, c1, batch, Hp, Wp, s));
   const AlFeat F{h->x1, h->f2, h->f3, h->f4, h->hc1, Hp, Wp, c1};
-  AL_RUN(launch_al_conv3x3(h->s8, 8, h->sh2, nullptr, h->s4a, 4, batch, Hp, Wp, AL_ACT_SELU, 0, 0, Hp, Wp, s));
-  AL_RUN(launch_al_conv3x3(h->s4a, 4, h->sh4, nullptr, h->s4b, 4, batch, Hp, Wp, AL_ACT_SELU, 0, 0, Hp, Wp, s));
-  AL_RUN(launch_al_conv3x3(h->s4b, 4, h->sh6, nullptr, h->score, 1, batch, Hp, Wp, AL_ACT_SIGMOID, pad_t, pad_l, H, W, s));  // unpad (ALN:672-673)
+  DIM_RUN(launch_al_conv3x3(h->s8, 8, h->sh2, nullptr, h->s4a, 4, batch, Hp, Wp, AL_ACT_SELU, 0, 0, Hp, Wp, s));
+  DIM_RUN(launch_al_conv3x3(h->s4a, 4, h->sh4, nullptr, h->s4b, 4, batch, Hp, Wp, AL_ACT_SELU, 0, 0, Hp, Wp, s));
+  DIM_RUN(launch_al_conv3x3(h->s4b, 4, h->sh6, nullptr, h->score, 1, batch, Hp, Wp, AL_ACT_SIGMOID, pad_t, pad_l, H, W, s));  // unpad (ALN:672-673)
   // DKD (ALN:123-244): NMS, border, threshold (mean fallback), n_limit, soft-argmax refinement
-  AL_RUN(launch_nms(h->score, h->nms, batch, H, W, r, s));
-  AL_RUN(launch_al_mean(h->score, batch, H * W, h->partial, h->mean, s));
+  DIM_RUN(launch_nms(h->score, h->nms, batch, H, W, r, s));
+  DIM_RUN(launch_al_mean(h->score, batch, H * W, h->partial, h->mean, s));
   if (h->cfg.detection_threshold > 0) {
-    AL_RUN(launch_select_ex(h->nms, batch, H, W, (float)h->cfg.detection_threshold, nullptr, r, h->rowcount, h->rowoff, h->ncand, h->cand_score, h->cand_idx, 1, s));
-    AL_RUN(launch_al_pick_threshold(h->ncand, h->mean, (float)h->cfg.detection_threshold, h->thr_eff, batch, s));
-    AL_RUN(launch_select_ex(h->nms, batch, H, W, 0.f, h->thr_eff, r, h->rowcount, h->rowoff, h->ncand, h->cand_score, h->cand_idx, 0, s));
+    DIM_RUN(launch_select_ex(h->nms, batch, H, W, (float)h->cfg.detection_threshold, nullptr, r, h->rowcount, h->rowoff, h->ncand, h->cand_score, h->cand_idx, 1, s));
+    DIM_RUN(launch_al_pick_threshold(h->ncand, h->mean, (float)h->cfg.detection_threshold, h->thr_eff, batch, s));
+    DIM_RUN(launch_select_ex(h->nms, batch, H, W, 0.f, h->thr_eff, r, h->rowcount, h->rowoff, h->ncand, h->cand_score, h->cand_idx, 0, s));
   } else if (h->cfg.max_num_keypoints <= 0) {
     // no threshold and no top-k (ALN:161-163): masks = nms_scores > mean score of the image
-    AL_RUN(launch_al_pick_threshold(h->ncand, h->mean, 0.f, h->thr_eff, batch, s));     // thr <= 0 -> the mean
-    AL_RUN(launch_select_ex(h->nms, batch, H, W, 0.f, h->thr_eff, r, h->rowcount, h->rowoff, h->ncand, h->cand_score, h->cand_idx, 0, s));
+    DIM_RUN(launch_al_pick_threshold(h->ncand, h->mean, 0.f, h->thr_eff, batch, s));     // thr <= 0 -> the mean
+    DIM_RUN(launch_select_ex(h->nms, batch, H, W, 0.f, h->thr_eff, r, h->rowcount, h->rowoff, h->ncand, h->cand_score, h->cand_idx, 0, s));
   } else {
     // top-k mode (ALN:150-151: topk over the border-cleared NMS map): every maximum is a candidate (the map is zero elsewhere, scores are
     // sigmoids > 0) and launch_topk keeps the max_num_keypoints highest, sorted; with FEWER maxima than that, zero-score pixels fill up
     // (launch_topk_zero_fill: which pixels torch.topk takes among the equal zeros is an artefact of its sort, not a rule)
-    AL_RUN(launch_select_ex(h->nms, batch, H, W, 0.f, nullptr, r, h->rowcount, h->rowoff, h->ncand, h->cand_score, h->cand_idx, 0, s));
+    DIM_RUN(launch_select_ex(h->nms, batch, H, W, 0.f, nullptr, r, h->rowcount, h->rowoff, h->ncand, h->cand_score, h->cand_idx, 0, s));
   }
   const bool topk_mode = !(h->cfg.detection_threshold > 0) && h->cfg.max_num_keypoints > 0;
   // n_limit (ALN:624-626): max_num_keypoints, or n_limit_max = 20000 (ALN:571) in the keep-all modes (bounded by the slot)
   const int n_limit = h->cfg.max_num_keypoints > 0 ? h->cfg.max_num_keypoints : (cap < 20000 ? cap : 20000);
-  AL_RUN(launch_topk(h->cand_score, h->cand_idx, h->ncand, batch, H, W, n_limit, cap, h->kpts_px, h->sc_tmp, n_kpts_dev, h->topk_keys, topk_mode ? 1 : 0, s));
-  if (topk_mode) AL_RUN(launch_topk_zero_fill(h->nms, batch, H, W, 0.f, r, n_limit, cap, h->kpts_px, h->sc_tmp, n_kpts_dev, s));
+  DIM_RUN(launch_topk(h->cand_score, h->cand_idx, h->ncand, batch, H, W, n_limit, cap, h->kpts_px, h->sc_tmp, n_kpts_dev, h->topk_keys, topk_mode ? 1 : 0, s));
+  if (topk_mode) DIM_RUN(launch_topk_zero_fill(h->nms, batch, H, W, 0.f, r, n_limit, cap, h->kpts_px, h->sc_tmp, n_kpts_dev, s));
   // Q8: DIM's "scores" are the dispersities (ALN:682 unpacks DKD's return in the wrong order)
-  AL_RUN(launch_al_dkd_refine(h->score, h->kpts_px, n_kpts_dev, h->kpts_norm, scores_dev, h->kscore, kpts_xy_dev, batch, H, W, cap, r, s));
+  DIM_RUN(launch_al_dkd_refine(h->score, h->kpts_px, n_kpts_dev, h->kpts_norm, scores_dev, h->kscore, kpts_xy_dev, batch, H, W, cap, r, s));
   // SDDH (ALN:503-558)
-  AL_RUN(launch_al_sddh_patches(F, h->kpts_norm, n_kpts_dev, h->patches, batch, H, W, pad_t, pad_l, cap, s));
+  DIM_RUN(launch_al_sddh_patches(F, h->kpts_norm, n_kpts_dev, h->patches, batch, H, W, pad_t, pad_l, cap, s));
   const int M = h->cfg.M, M2 = 2 * M, PK = dim * 9;
   {
     GemmArgs g;
     g.A0 = h->patches; g.lda0 = PK; g.strideA0 = (long long)cap * PK; g.B = h->dh_o0_w; g.ldb = M2; g.bias = h->dh_o0_b;
     g.C = h->hidden; g.ldc = M2; g.strideC = (long long)cap * M2; g.M = cap; g.N = M2; g.K = PK; g.rows = n_kpts_dev;
-    AL_RUN(gemm(g, h->g_o0, batch));
+    DIM_RUN(gemm(g, h->g_o0, batch));
   }
-  AL_RUN(launch_al_sddh_sample(F, h->kpts_norm, n_kpts_dev, h->hidden, h->dh_o2_w, h->dh_o2_b, h->feats, M, batch, H, W, pad_t, pad_l, cap, s));
+  DIM_RUN(launch_al_sddh_sample(F, h->kpts_norm, n_kpts_dev, h->hidden, h->dh_o2_w, h->dh_o2_b, h->feats, M, batch, H, W, pad_t, pad_l, cap, s));
   {
     GemmArgs g;  // sf_conv 1x1 (dim -> dim) + SELU over the M sampled positions of every keypoint
     g.A0 = h->feats; g.lda0 = dim; g.strideA0 = (long long)cap * M * dim; g.B = h->dh_sf; g.ldb = dim;
     g.C = h->feats2; g.ldc = dim; g.strideC = (long long)cap * M * dim; g.M = cap * M; g.N = dim; g.K = dim;
     g.rows = n_kpts_dev; g.rows_scale = M; g.relu = 2;
-    AL_RUN(gemm(g, h->g_sf, batch));
+    DIM_RUN(gemm(g, h->g_sf, batch));
   }
   {
     GemmArgs g;  // einsum("ncp,pcd->nd") with agg_weights [p][c][d] == [n][p*dim+c] x [p*dim+c][d]
     g.A0 = h->feats2; g.lda0 = M * dim; g.strideA0 = (long long)cap * M * dim; g.B = h->dh_agg; g.ldb = dim;
     g.C = desc_dev; g.ldc = dim; g.strideC = (long long)cap * dim; g.M = cap; g.N = dim; g.K = M * dim; g.rows = n_kpts_dev;
-    AL_RUN(gemm(g, h->g_agg, batch));
+    DIM_RUN(gemm(g, h->g_agg, batch));
   }
-  AL_RUN(launch_al_normalize_rows(desc_dev, n_kpts_dev, batch, cap, dim, s));
-#undef AL_RUN
+  DIM_RUN(launch_al_normalize_rows(desc_dev, n_kpts_dev, batch, cap, dim, s));
   h->last_hp = Hp; h->last_wp = Wp; h->last_h = H; h->last_w = W; h->last_batch = batch;
   return 0;
 }

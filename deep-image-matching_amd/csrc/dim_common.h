@@ -373,6 +373,7 @@ int dim_upload_split(DimHandleBase* b, SplitWeights* sw, const std::vector<unsig
 int dim_upload_gemm_split(DimHandleBase* b, SplitWeights* sw, const float* w_kn, int K, int N, int n_pad, int mode, int kperm = 0);
 void dim_handle_release(DimHandleBase* b);   // frees the allocations (the handle object itself is the caller's)
 #define DIM_TRY(x) do { if ((x) != 0) return -1; } while (0)   // create functions hold the handle in a std::unique_ptr with its destroy as deleter
+#define DIM_RUN(x) do { int rc__ = (x); if (rc__ != 0) return rc__; } while (0)   // run functions: a launcher's return code is passed on
 void dim_tune_scope_set(const DimTune* t);     // api_ops.hip (thread-local)
 const DimTune* dim_tune_scope_get();
 struct DimTuneScope {

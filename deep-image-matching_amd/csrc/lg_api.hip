@@ -254,13 +254,12 @@ int dim_lg_match(dim_lg* h, const float* kpts_tab_dev, const float* desc_tab_dev
   st.nsel = Nsel;
   const long long s256 = (long long)N * 256, s512 = (long long)N * 512, s768 = (long long)N * 768;
   const bool early = h->cfg.depth_confidence > 0, prune = h->cfg.width_confidence > 0;  // LGN:480-481
-#define LG_RUN(x) do { int rc__ = (x); if (rc__ != 0) return rc__; } while (0)
   const int pmode = dim_precision_mode();  // 2 fp16x3 (default) / 1 bf16x6: fp32-accurate products on the 16-bit matrix cores; 0 fp32 MFMA
   const bool x6 = pmode != 0;
   // fp16x3 range guard (dim_common.h): every producer of a value that a later split consumes reports max|x| > 4094
   auto sat = [&](int site) -> unsigned* { return pmode == 2 ? dim_sat_counter(site) : nullptr; };
   st.sat_qkv = sat(DIM_SAT_LG_QKV); st.sat_ffn = sat(DIM_SAT_LG_FFN);
-  LG_RUN(launch_lg_init(st, kpts_tab_dev, desc_tab_dev, n_tab_dev, size_tab_dev, pair_idx_dev, cap, h->input_dim, h->Wr,
+  DIM_RUN(launch_lg_init(st, kpts_tab_dev, desc_tab_dev, n_tab_dev, size_tab_dev, pair_idx_dev, cap, h->input_dim, h->Wr,
                         h->input_dim == 256 ? 1 : 0, sat(DIM_SAT_LG_INPUT), s));
   const bool fold = x6 && dim_fold_out_proj();  // split modes: out_proj folded into ffn.0 (one GEMM less per block)
   // fp16x3 at batch sizes that fill the GPU with 64-row blocks: LayerNorm + GELU run in ffn.0's epilogue (dim_tune_set key 11)
@@ -308,7 +307,7 @@ int dim_lg_match(dim_lg* h, const float* kpts_tab_dev, const float* desc_tab_dev
     g.A0 = desc_tab_dev; g.lda0 = h->input_dim; g.strideA0 = (long long)cap * h->input_dim; g.a_idx = pair_idx_dev;
     g.B = h->inproj_w; g.ldb = 256; g.bias = h->inproj_b; g.C = st.desc; g.ldc = 256; g.strideC = s256;
     g.M = Nsel; g.N = 256; g.K = h->input_dim; g.rows = st.n_cur; g.sat = sat(DIM_SAT_LG_INPUT);
-    LG_RUN(launch_gemm(g, I, s));
+    DIM_RUN(launch_gemm(g, I, s));
   }
   // ---- assignment (LGN:540-542).  tag = layer + 1: the pairs that stopped at that layer, with its weights (gated launches after every layer that may
   // stop pairs).  tag = 0, the DEFERRED form of adaptive depth (round 6): a stopped pair's descriptors, counts and index tables are frozen — every later
@@ -324,17 +323,17 @@ int dim_lg_match(dim_lg* h, const float* kpts_tab_dev, const float* desc_tab_dev
       g.sat = sat(DIM_SAT_LG_DESC);   // guarded: the similarity splits it
       if (tag == 0) { g.set_split(h->L[0].proj_x[pmode]); g.bias = h->L[0].proj_b; g.layer_tab = h->proj_tab[pmode]; }   // (shape fields from layer 0; pointers per item)
       else { g.B = w->proj_w; g.ldb = 256; g.bias = w->proj_b; if (x6) g.set_split(w->proj_x[pmode]); }
-      if (x6) LG_RUN(launch_gemm_x6(g, I, s)); else LG_RUN(launch_gemm(g, I, s));
+      if (x6) DIM_RUN(launch_gemm_x6(g, I, s)); else DIM_RUN(launch_gemm(g, I, s));
     }
     GemmArgs g;
     g.A0 = st.md; g.lda0 = 256; g.strideA0 = 2 * s256; g.B = st.md + s256; g.ldb = 256; g.strideB = 2 * s256; g.bt = 1;
     g.C = st.sim; g.ldc = N; g.strideC = (long long)N * N; g.M = Nsel; g.N = Nsel; g.K = 256;
     g.rows = st.n_cur; g.rows_mul = 2; g.rows_off = 0; g.cols = st.n_cur; g.cols_mul = 2; g.cols_off = 1;
     g.flag = st.done; g.flag_shift = 0; g.flag_eq = tag; g.flag_any = tag == 0 ? 1 : 0;
-    if (x6) LG_RUN(launch_gemm_x6_nt(g, n_pairs, pmode, s));   // split-precision on the 16-bit matrix cores like every other product
-    else LG_RUN(launch_gemm(g, n_pairs, s));
-    LG_RUN(launch_lg_assign_stats(st, tag, tag == 0 ? h->match_w_all : w->match_w, tag == 0 ? h->match_b_all : w->match_b, s));
-    LG_RUN(launch_lg_assign_argmax(st, tag, dense_scores_dev, s));
+    if (x6) DIM_RUN(launch_gemm_x6_nt(g, n_pairs, pmode, s));   // split-precision on the 16-bit matrix cores like every other product
+    else DIM_RUN(launch_gemm(g, n_pairs, s));
+    DIM_RUN(launch_lg_assign_stats(st, tag, tag == 0 ? h->match_w_all : w->match_w, tag == 0 ? h->match_b_all : w->match_b, s));
+    DIM_RUN(launch_lg_assign_argmax(st, tag, dense_scores_dev, s));
     return 0;
   };
   // ---- one or two pairs per call (the plugin hooks) with adaptive depth: the HOST follows the stop flags two layers behind the device.  Every launch
@@ -368,56 +367,55 @@ int dim_lg_match(dim_lg* h, const float* kpts_tab_dev, const float* desc_tab_dev
       if (!seen) follow = false;   // the device is not making progress while we wait (a stream held back by the caller?): enqueue the rest without looking
     }
     // ---- self block (LGN:146-159) ----
-    if (fuse_kv) LG_RUN(gemm_qkv(w.qkv_x, w.qkv_b, 768, 1, true));
-    else LG_RUN(gemm_items(st.desc, 256, s256, nullptr, 0, 0, 0, w.qkv_w, w.qkv_x, 768, w.qkv_b, nullptr, st.qkv, 768, s768, 768, 256, 0, st.sat_qkv));
-    if (!x6) LG_RUN(launch_lg_rotary(st, s));  // the bf16x6 attention applies the rotary embedding while it loads q / pre-splits k
+    if (fuse_kv) DIM_RUN(gemm_qkv(w.qkv_x, w.qkv_b, 768, 1, true));
+    else DIM_RUN(gemm_items(st.desc, 256, s256, nullptr, 0, 0, 0, w.qkv_w, w.qkv_x, 768, w.qkv_b, nullptr, st.qkv, 768, s768, 768, 256, 0, st.sat_qkv));
+    if (!x6) DIM_RUN(launch_lg_rotary(st, s));  // the bf16x6 attention applies the rotary embedding while it loads q / pre-splits k
     dim_prof_begin(DIM_PROF_LG_SELF_ATTN, s);
-    LG_RUN(launch_lg_attention(st, 0, s, fuse_kv ? 1 : 0));
+    DIM_RUN(launch_lg_attention(st, 0, s, fuse_kv ? 1 : 0));
     dim_prof_end(DIM_PROF_LG_SELF_ATTN, s);
-    if (fuse_ffn) LG_RUN(ffn_fused(w.sffn0f_x, w.sffn0f_b, w.sln_w, w.sln_b, w.sffn3p_x, w.sffn3_b));
+    if (fuse_ffn) DIM_RUN(ffn_fused(w.sffn0f_x, w.sffn0f_b, w.sln_w, w.sln_b, w.sffn3p_x, w.sffn3_b));
     else {
     if (fold) {  // out_proj folded into ffn.0: A = [desc | ctx]
-      LG_RUN(gemm_items(st.desc, 256, s256, st.ctx, 256, s256, 256, nullptr, w.sffn0f_x, 512, w.sffn0f_b, nullptr, st.hid, 512, s512, 512, 512, 0,
+      DIM_RUN(gemm_items(st.desc, 256, s256, st.ctx, 256, s256, 256, nullptr, w.sffn0f_x, 512, w.sffn0f_b, nullptr, st.hid, 512, s512, 512, 512, 0,
                         fuse_ln ? st.sat_ffn : nullptr, fuse_ln ? w.sln_w : nullptr, fuse_ln ? w.sln_b : nullptr));
     } else {
-      LG_RUN(gemm_items(st.ctx, 256, s256, nullptr, 0, 0, 0, w.out_w, w.out_x, 256, w.out_b, nullptr, st.msg, 256, s256, 256, 256, 0));
-      LG_RUN(gemm_items(st.desc, 256, s256, st.msg, 256, s256, 256, w.sffn0_w, w.sffn0_x, 512, w.sffn0_b, nullptr, st.hid, 512, s512, 512, 512, 0));
+      DIM_RUN(gemm_items(st.ctx, 256, s256, nullptr, 0, 0, 0, w.out_w, w.out_x, 256, w.out_b, nullptr, st.msg, 256, s256, 256, 256, 0));
+      DIM_RUN(gemm_items(st.desc, 256, s256, st.msg, 256, s256, 256, w.sffn0_w, w.sffn0_x, 512, w.sffn0_b, nullptr, st.hid, 512, s512, 512, 512, 0));
     }
-    if (!(fold && fuse_ln)) LG_RUN(launch_lg_ln_gelu(st, w.sln_w, w.sln_b, s));
-    LG_RUN(gemm_items(st.hid, 512, s512, nullptr, 0, 0, 0, w.sffn3_w, w.sffn3_x, 256, w.sffn3_b, st.desc, st.desc, 256, s256, 256, 512, 0, sat(DIM_SAT_LG_DESC)));
+    if (!(fold && fuse_ln)) DIM_RUN(launch_lg_ln_gelu(st, w.sln_w, w.sln_b, s));
+    DIM_RUN(gemm_items(st.hid, 512, s512, nullptr, 0, 0, 0, w.sffn3_w, w.sffn3_x, 256, w.sffn3_b, st.desc, st.desc, 256, s256, 256, 512, 0, sat(DIM_SAT_LG_DESC)));
     }
     // ---- cross block (LGN:186-211) ----
-    if (fuse_kv) LG_RUN(gemm_qkv(w.cqkv_x, w.cqkv_b, 512, 0, false));
-    else LG_RUN(gemm_items(st.desc, 256, s256, nullptr, 0, 0, 0, w.cqkv_w, w.cqkv_x, 512, w.cqkv_b, nullptr, st.qkv, 768, s768, 512, 256, 0, st.sat_qkv));
+    if (fuse_kv) DIM_RUN(gemm_qkv(w.cqkv_x, w.cqkv_b, 512, 0, false));
+    else DIM_RUN(gemm_items(st.desc, 256, s256, nullptr, 0, 0, 0, w.cqkv_w, w.cqkv_x, 512, w.cqkv_b, nullptr, st.qkv, 768, s768, 512, 256, 0, st.sat_qkv));
     dim_prof_begin(DIM_PROF_LG_CROSS_ATTN, s);
-    LG_RUN(launch_lg_attention(st, 1, s, fuse_kv ? 1 : 0));
+    DIM_RUN(launch_lg_attention(st, 1, s, fuse_kv ? 1 : 0));
     dim_prof_end(DIM_PROF_LG_CROSS_ATTN, s);
-    if (fuse_ffn) LG_RUN(ffn_fused(w.cffn0f_x, w.cffn0f_b, w.cln_w, w.cln_b, w.cffn3p_x, w.cffn3_b));
+    if (fuse_ffn) DIM_RUN(ffn_fused(w.cffn0f_x, w.cffn0f_b, w.cln_w, w.cln_b, w.cffn3p_x, w.cffn3_b));
     else {
     if (fold) {
-      LG_RUN(gemm_items(st.desc, 256, s256, st.ctx, 256, s256, 256, nullptr, w.cffn0f_x, 512, w.cffn0f_b, nullptr, st.hid, 512, s512, 512, 512, 0,
+      DIM_RUN(gemm_items(st.desc, 256, s256, st.ctx, 256, s256, 256, nullptr, w.cffn0f_x, 512, w.cffn0f_b, nullptr, st.hid, 512, s512, 512, 512, 0,
                         fuse_ln ? st.sat_ffn : nullptr, fuse_ln ? w.cln_w : nullptr, fuse_ln ? w.cln_b : nullptr));
     } else {
-      LG_RUN(gemm_items(st.ctx, 256, s256, nullptr, 0, 0, 0, w.cout_w, w.cout_x, 256, w.cout_b, nullptr, st.msg, 256, s256, 256, 256, 0));
-      LG_RUN(gemm_items(st.desc, 256, s256, st.msg, 256, s256, 256, w.cffn0_w, w.cffn0_x, 512, w.cffn0_b, nullptr, st.hid, 512, s512, 512, 512, 0));
+      DIM_RUN(gemm_items(st.ctx, 256, s256, nullptr, 0, 0, 0, w.cout_w, w.cout_x, 256, w.cout_b, nullptr, st.msg, 256, s256, 256, 256, 0));
+      DIM_RUN(gemm_items(st.desc, 256, s256, st.msg, 256, s256, 256, w.cffn0_w, w.cffn0_x, 512, w.cffn0_b, nullptr, st.hid, 512, s512, 512, 512, 0));
     }
-    if (!(fold && fuse_ln)) LG_RUN(launch_lg_ln_gelu(st, w.cln_w, w.cln_b, s));
-    LG_RUN(gemm_items(st.hid, 512, s512, nullptr, 0, 0, 0, w.cffn3_w, w.cffn3_x, 256, w.cffn3_b, st.desc, st.desc, 256, s256, 256, 512, 0, sat(DIM_SAT_LG_DESC)));
+    if (!(fold && fuse_ln)) DIM_RUN(launch_lg_ln_gelu(st, w.cln_w, w.cln_b, s));
+    DIM_RUN(gemm_items(st.hid, 512, s512, nullptr, 0, 0, 0, w.cffn3_w, w.cffn3_x, 256, w.cffn3_b, st.desc, st.desc, 256, s256, 256, 512, 0, sat(DIM_SAT_LG_DESC)));
     }
     // ---- adaptive depth / width (LGN:494-516) ----
     const bool last = (i == Lr - 1);
     if (!last && (early || prune))
-      LG_RUN(launch_lg_confidence(st, w.tok_w, w.tok_b, w.match_w, w.match_b, h->thr[i], early ? 1 : 0, s));
+      DIM_RUN(launch_lg_confidence(st, w.tok_w, w.tok_b, w.match_w, w.match_b, h->thr[i], early ? 1 : 0, s));
     if (last || early)
-      LG_RUN(launch_lg_decide(st, i, (float)h->cfg.depth_confidence, early ? 1 : 0, last ? 1 : 0, s, follow ? h->done_host + (size_t)i * mstride : nullptr, h->max_pairs, seq));
-    if ((last || early) && !defer) LG_RUN(assignment(i + 1, &w));   // the pairs that stopped at this layer (LGN:540-542)
+      DIM_RUN(launch_lg_decide(st, i, (float)h->cfg.depth_confidence, early ? 1 : 0, last ? 1 : 0, s, follow ? h->done_host + (size_t)i * mstride : nullptr, h->max_pairs, seq));
+    if ((last || early) && !defer) DIM_RUN(assignment(i + 1, &w));   // the pairs that stopped at this layer (LGN:540-542)
     if (!last && prune)
-      LG_RUN(launch_lg_prune(st, i, h->cfg.width_confidence, h->thr[i], early ? 1 : 0, h->cfg.pruning_min_kpts, s));
+      DIM_RUN(launch_lg_prune(st, i, h->cfg.width_confidence, h->thr[i], early ? 1 : 0, h->cfg.pruning_min_kpts, s));
   }
-  if (defer) LG_RUN(assignment(0, nullptr));
-  LG_RUN(launch_lg_finalize(st, Lr, prune ? 1 : 0, (float)h->cfg.filter_threshold, N, (long long*)matches_dev, mscores_dev,
+  if (defer) DIM_RUN(assignment(0, nullptr));
+  DIM_RUN(launch_lg_finalize(st, Lr, prune ? 1 : 0, (float)h->cfg.filter_threshold, N, (long long*)matches_dev, mscores_dev,
                             n_matches_dev, matches01_dev, mscores01_dev, stop_dev, prune01_dev, s));
-#undef LG_RUN
   return 0;
 }
 

@@ -125,17 +125,16 @@ int lgl_match(dim_lg* h, const float* kpts_tab_dev, const float* desc_tab_dev, c
   st.nsel = Nsel;
   const long long s96 = (long long)N * D, s192 = (long long)N * D2, s288 = (long long)N * D3;
   const bool early = h->cfg.depth_confidence > 0, prune = h->cfg.width_confidence > 0;  // LGN:480-481
-#define LG_RUN(x) do { int rc__ = (x); if (rc__ != 0) return rc__; } while (0)
   // fp16x3 range guard (dim_common.h): the sites of the 256-wide path, fed by the same producers
   auto sat = [&](int site) -> unsigned* { return pmode == 2 ? dim_sat_counter(site) : nullptr; };
   st.sat_qkv = sat(DIM_SAT_LG_QKV); st.sat_ffn = sat(DIM_SAT_LG_FFN);
-  LG_RUN(launch_lgl_init(st, kpts_tab_dev, n_tab_dev, size_tab_dev, pair_idx_dev, cap, h->Wr, s));
+  DIM_RUN(launch_lgl_init(st, kpts_tab_dev, n_tab_dev, size_tab_dev, pair_idx_dev, cap, h->Wr, s));
   {  // input_proj (LGN:473-474) straight from the feature table
     GemmArgs g;
     g.A0 = desc_tab_dev; g.lda0 = h->input_dim; g.strideA0 = (long long)cap * h->input_dim; g.a_idx = pair_idx_dev;
     g.B = h->inproj_w; g.ldb = D; g.bias = h->inproj_b; g.C = st.desc; g.ldc = D; g.strideC = s96;
     g.M = Nsel; g.N = D; g.K = h->input_dim; g.rows = st.n_cur; g.sat = sat(DIM_SAT_LG_INPUT);
-    LG_RUN(launch_gemm(g, I, s));
+    DIM_RUN(launch_gemm(g, I, s));
   }
   // C[item] = [A | A1] * W + bias (+ R) over the live rows of the items whose pair is still iterating
   auto gemm_items = [&](const float* A, int lda, long long sA, const float* A1, int lda1, long long sA1, int ksplit, const SplitWeights* Bx,
@@ -151,47 +150,46 @@ int lgl_match(dim_lg* h, const float* kpts_tab_dev, const float* desc_tab_dev, c
   // out_proj / to_out, ffn.0 on [desc | message], LayerNorm + GELU, ffn.3 + residual (LGN:139-144,159,209)
   auto feed_forward = [&](const SplitWeights* out_x, const float* out_b, const SplitWeights* f0_x, const float* f0_b, const float* ln_w, const float* ln_b,
                           const SplitWeights* f3_x, const float* f3_b) -> int {
-    LG_RUN(gemm_items(st.ctx, D, s96, nullptr, 0, 0, 0, out_x, out_b, nullptr, st.msg, D, s96, D, D, 0, nullptr));
-    LG_RUN(gemm_items(st.desc, D, s96, st.msg, D, s96, D, f0_x, f0_b, nullptr, st.hid, D2, s192, D2, D2, 0, nullptr));
-    LG_RUN(launch_lgl_ln_gelu(st, ln_w, ln_b, s));
+    DIM_RUN(gemm_items(st.ctx, D, s96, nullptr, 0, 0, 0, out_x, out_b, nullptr, st.msg, D, s96, D, D, 0, nullptr));
+    DIM_RUN(gemm_items(st.desc, D, s96, st.msg, D, s96, D, f0_x, f0_b, nullptr, st.hid, D2, s192, D2, D2, 0, nullptr));
+    DIM_RUN(launch_lgl_ln_gelu(st, ln_w, ln_b, s));
     return gemm_items(st.hid, D2, s192, nullptr, 0, 0, 0, f3_x, f3_b, st.desc, st.desc, D, s96, D, D2, 0, sat(DIM_SAT_LG_DESC));
   };
   // assignment (LGN:540-542) for the pairs that stopped at layer tag - 1, with its weights
   auto assignment = [&](int tag, const LayerW& w) -> int {
-    LG_RUN(gemm_items(st.desc, D, s96, nullptr, 0, 0, 0, w.proj_x, w.proj_b, nullptr, st.md, D, s96, D, D, tag, nullptr));
-    LG_RUN(launch_lgl_scale_md(st, tag, sat(DIM_SAT_LG_DESC), s));   // guarded: the similarity splits it
+    DIM_RUN(gemm_items(st.desc, D, s96, nullptr, 0, 0, 0, w.proj_x, w.proj_b, nullptr, st.md, D, s96, D, D, tag, nullptr));
+    DIM_RUN(launch_lgl_scale_md(st, tag, sat(DIM_SAT_LG_DESC), s));   // guarded: the similarity splits it
     GemmArgs g;
     g.A0 = st.md; g.lda0 = D; g.strideA0 = 2 * s96; g.B = st.md + s96; g.ldb = D; g.strideB = 2 * s96; g.bt = 1;
     g.C = st.sim; g.ldc = N; g.strideC = (long long)N * N; g.M = Nsel; g.N = Nsel; g.K = D;
     g.rows = st.n_cur; g.rows_mul = 2; g.rows_off = 0; g.cols = st.n_cur; g.cols_mul = 2; g.cols_off = 1;
     g.flag = st.done; g.flag_shift = 0; g.flag_eq = tag;
-    LG_RUN(launch_gemm_x6_nt(g, n_pairs, pmode, s));
-    LG_RUN(launch_lg_assign_stats(st, tag, w.match_w, w.match_b, s));
+    DIM_RUN(launch_gemm_x6_nt(g, n_pairs, pmode, s));
+    DIM_RUN(launch_lg_assign_stats(st, tag, w.match_w, w.match_b, s));
     return launch_lg_assign_argmax(st, tag, dense_scores_dev, s);
   };
   for (int i = 0; i < Lr; ++i) {
     const LayerW& w = h->L[i];
     // ---- self block (LGN:146-159) ----
-    LG_RUN(gemm_items(st.desc, D, s96, nullptr, 0, 0, 0, w.qkv_x, w.qkv_b, nullptr, st.qkv, D3, s288, D3, D, 0, st.sat_qkv));
+    DIM_RUN(gemm_items(st.desc, D, s96, nullptr, 0, 0, 0, w.qkv_x, w.qkv_b, nullptr, st.qkv, D3, s288, D3, D, 0, st.sat_qkv));
     dim_prof_begin(DIM_PROF_LG_SELF_ATTN, s);
-    LG_RUN(launch_lgl_attention(st, 0, s));
+    DIM_RUN(launch_lgl_attention(st, 0, s));
     dim_prof_end(DIM_PROF_LG_SELF_ATTN, s);
-    LG_RUN(feed_forward(w.out_x, w.out_b, w.sffn0_x, w.sffn0_b, w.sln_w, w.sln_b, w.sffn3_x, w.sffn3_b));
+    DIM_RUN(feed_forward(w.out_x, w.out_b, w.sffn0_x, w.sffn0_b, w.sln_w, w.sln_b, w.sffn3_x, w.sffn3_b));
     // ---- cross block (LGN:186-211) ----
-    LG_RUN(gemm_items(st.desc, D, s96, nullptr, 0, 0, 0, w.cqkv_x, w.cqkv_b, nullptr, st.qkv, D3, s288, D2, D, 0, st.sat_qkv));
+    DIM_RUN(gemm_items(st.desc, D, s96, nullptr, 0, 0, 0, w.cqkv_x, w.cqkv_b, nullptr, st.qkv, D3, s288, D2, D, 0, st.sat_qkv));
     dim_prof_begin(DIM_PROF_LG_CROSS_ATTN, s);
-    LG_RUN(launch_lgl_attention(st, 1, s));
+    DIM_RUN(launch_lgl_attention(st, 1, s));
     dim_prof_end(DIM_PROF_LG_CROSS_ATTN, s);
-    LG_RUN(feed_forward(w.cout_x, w.cout_b, w.cffn0_x, w.cffn0_b, w.cln_w, w.cln_b, w.cffn3_x, w.cffn3_b));
+    DIM_RUN(feed_forward(w.cout_x, w.cout_b, w.cffn0_x, w.cffn0_b, w.cln_w, w.cln_b, w.cffn3_x, w.cffn3_b));
     // ---- adaptive depth / width (LGN:494-516) ----
     const bool last = (i == Lr - 1);
-    if (!last && (early || prune)) LG_RUN(launch_lgl_confidence(st, w.tok_w, w.tok_b, w.match_w, w.match_b, h->thr[i], early ? 1 : 0, s));
-    if (last || early) LG_RUN(launch_lg_decide(st, i, (float)h->cfg.depth_confidence, early ? 1 : 0, last ? 1 : 0, s));
-    if (last || early) LG_RUN(assignment(i + 1, w));
-    if (!last && prune) LG_RUN(launch_lg_prune(st, i, h->cfg.width_confidence, h->thr[i], early ? 1 : 0, h->cfg.pruning_min_kpts, s));
+    if (!last && (early || prune)) DIM_RUN(launch_lgl_confidence(st, w.tok_w, w.tok_b, w.match_w, w.match_b, h->thr[i], early ? 1 : 0, s));
+    if (last || early) DIM_RUN(launch_lg_decide(st, i, (float)h->cfg.depth_confidence, early ? 1 : 0, last ? 1 : 0, s));
+    if (last || early) DIM_RUN(assignment(i + 1, w));
+    if (!last && prune) DIM_RUN(launch_lg_prune(st, i, h->cfg.width_confidence, h->thr[i], early ? 1 : 0, h->cfg.pruning_min_kpts, s));
   }
-  LG_RUN(launch_lg_finalize(st, Lr, prune ? 1 : 0, (float)h->cfg.filter_threshold, N, (long long*)matches_dev, mscores_dev, n_matches_dev,
+  DIM_RUN(launch_lg_finalize(st, Lr, prune ? 1 : 0, (float)h->cfg.filter_threshold, N, (long long*)matches_dev, mscores_dev, n_matches_dev,
                             matches01_dev, mscores01_dev, stop_dev, prune01_dev, s));
-#undef LG_RUN
   return 0;
 }

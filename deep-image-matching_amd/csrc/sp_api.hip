@@ -209,8 +209,7 @@ int dim_sp_extract(dim_sp* h, const float* images_dev, int batch, int H, int W, 
   hipStream_t s = (hipStream_t)stream;
   const int H2 = H / 2, W2 = W / 2, H4 = H2 / 2, W4 = W2 / 2, hh = H4 / 2, ww = W4 / 2;  // floor at every pool (Q12)
   const int H8 = hh * 8, W8 = ww * 8;
-#define SP_RUN(x) do { int rc__ = (x); if (rc__ != 0) return rc__; } while (0)
-#define SP_SITE(id, x) do { dim_prof_begin(id, s); SP_RUN(x); dim_prof_end(id, s); } while (0)
+#define SP_SITE(id, x) do { dim_prof_begin(id, s); DIM_RUN(x); dim_prof_end(id, s); } while (0)
   const int pmode = dim_precision_mode();  // 2 (default) fp16x3 / 1 bf16x6: fp32-accurate products on the 16-bit matrix cores; 0: fp32 MFMA
   const bool x6 = pmode != 0;
   const int bn = h->bn ? 1 : 0;
@@ -242,7 +241,7 @@ int dim_sp_extract(dim_sp* h, const float* images_dev, int batch, int H, int W, 
   if (x6 && dim_fuse_conv1a()) {  // conv1a evaluated inside conv1b's halo staging: its 64-channel full-resolution map never exists
     SP_SITE(DIM_PROF_SP_CONV1B, launch_conv3x3_x6_fused1a(images_dev, h->wk[0], h->bias[0], h->wsp[pmode][1], h->bias[1], h->b1, batch, H, W, 64, 1, 1, planes ? 1 : 0, s, sat_enc, sat_img, bn));
   } else {
-    if (!h->a1) SP_RUN(dim_dev_alloc(&h->base, &h->a1, (size_t)h->max_batch * h->max_h * h->max_w * 64));
+    if (!h->a1) DIM_RUN(dim_dev_alloc(&h->base, &h->a1, (size_t)h->max_batch * h->max_h * h->max_w * 64));
     SP_SITE(DIM_PROF_SP_CONV1A, launch_conv1a(images_dev, h->wk[0], h->bias[0], h->a1, batch, H, W, s));
     SP_SITE(DIM_PROF_SP_CONV1B, conv(1, h->a1, h->b1, H, W, 64, 64, 1));
   }
@@ -273,18 +272,18 @@ int dim_sp_extract(dim_sp* h, const float* images_dev, int batch, int H, int W, 
     h->head_fused = pmode == 2 && dim_fuse_sp_head();
     if (h->head_fused) {
       g.set_split(h->wsp[pmode][9]); g.d2s_out = h->smap; g.d2s_h = hh; g.d2s_w = ww;
-      SP_RUN(launch_gemm_x6(g, 1, s));
+      DIM_RUN(launch_gemm_x6(g, 1, s));
     } else {
-      if (x6) { g.set_split(h->wsp[pmode][9]); SP_RUN(launch_gemm_x6(g, 1, s)); }
-      else SP_RUN(launch_gemm(g, 1, s));
-      SP_RUN(launch_softmax_d2s(h->logits, h->smap, batch, hh, ww, s));
+      if (x6) { g.set_split(h->wsp[pmode][9]); DIM_RUN(launch_gemm_x6(g, 1, s)); }
+      else DIM_RUN(launch_gemm(g, 1, s));
+      DIM_RUN(launch_softmax_d2s(h->logits, h->smap, batch, hh, ww, s));
     }
   }
-  SP_RUN(launch_nms(h->smap, h->nms, batch, H8, W8, h->cfg.nms_radius, s));
+  DIM_RUN(launch_nms(h->smap, h->nms, batch, H8, W8, h->cfg.nms_radius, s));
   // selection (SPN:183-210)
-  SP_RUN(launch_select(h->nms, batch, H8, W8, h->cfg.keypoint_threshold, h->cfg.remove_borders, h->rowcount, h->rowoff,
+  DIM_RUN(launch_select(h->nms, batch, H8, W8, h->cfg.keypoint_threshold, h->cfg.remove_borders, h->rowcount, h->rowoff,
                        h->ncand, h->cand_score, h->cand_idx, s));
-  SP_RUN(launch_topk(h->cand_score, h->cand_idx, h->ncand, batch, H8, W8, h->cfg.max_keypoints, h->capacity, kpts_xy_dev,
+  DIM_RUN(launch_topk(h->cand_score, h->cand_idx, h->ncand, batch, H8, W8, h->cfg.max_keypoints, h->capacity, kpts_xy_dev,
                      scores_dev, n_kpts_dev, h->topk_keys, 0, s));
   // descriptor head (SPN:213-221)
   if (planes) SP_SITE(DIM_PROF_SP_CONVDA, convp(10, h->x, h->da, hh, ww, 128, 256, 0, 1, 0));
@@ -293,12 +292,11 @@ int dim_sp_extract(dim_sp* h, const float* images_dev, int batch, int H, int W, 
     GemmArgs g;
     g.A0 = h->da; g.lda0 = 256; g.B = h->wk[11]; g.ldb = 256; g.bias = h->bias[11];
     g.C = h->dd; g.ldc = 256; g.M = batch * hh * ww; g.N = 256; g.K = 256;
-    if (x6) { g.set_split(h->wsp[pmode][11]); SP_RUN(launch_gemm_x6(g, 1, s)); }
-    else SP_RUN(launch_gemm(g, 1, s));
+    if (x6) { g.set_split(h->wsp[pmode][11]); DIM_RUN(launch_gemm_x6(g, 1, s)); }
+    else DIM_RUN(launch_gemm(g, 1, s));
   }
-  SP_RUN(launch_sample_desc(h->dd, kpts_xy_dev, n_kpts_dev, desc_dev, batch, hh, ww, h->capacity, h->cfg.fix_sampling, s));
+  DIM_RUN(launch_sample_desc(h->dd, kpts_xy_dev, n_kpts_dev, desc_dev, batch, hh, ww, h->capacity, h->cfg.fix_sampling, s));
 #undef SP_SITE
-#undef SP_RUN
   h->last_h = hh; h->last_w = ww; h->last_batch = batch;
   return 0;
 }

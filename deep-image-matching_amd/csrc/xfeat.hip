@@ -1,8 +1,7 @@
 // XFeat (thirdparty/accelerated_features/modules/{xfeat,model,interpolator}.py = XFM / XFN / XFI) kernels for gfx950: preparation (resize, channel
-// mean, InstanceNorm), the bandwidth-bound stem as direct fp32 convolutions over LDS halo tiles, the trunk as an implicit GEMM on the matrix
-// cores (alike.hip's conventions + stride + the 8 x 8 unfold operand load), the head tails, the single-pass NMS / key map and the bicubic sparse tail.
-// Arithmetic of the trunk: fp16x3 on v_mfma_f32_32x32x16_f16 (SplitMma<2>, dim_common.h) by default, fp32 MFMA (v_mfma_f32_32x32x2_f32) otherwise;
-// everything else is fp32 (fp64 for the image statistics) in every mode.  Every reduction has a fixed order; no floating-point atomics.
+// mean, InstanceNorm), the bandwidth-bound stem as direct fp32 convolutions over LDS halo tiles, the head tails, the single-pass NMS / key map and
+// the bicubic sparse tail.  The trunk is nhwc_conv.hip's implicit GEMM on the matrix cores (stride 2 and the 8 x 8 unfold operand load included).
+// Everything here is fp32 (fp64 for the image statistics) in every mode.  Every reduction has a fixed order; no floating-point atomics.
 #include "xfeat_kernels.h"
 
 namespace {
@@ -234,101 +233,6 @@ __global__ __launch_bounds__(256) void xf_stem4_kernel(const float* __restrict__
   sat_report(sat, track);
 }
 
-// ---------------------------------------------------------------------------
-// Trunk convolution: alike.hip's ak_conv_kernel (one wave = 8 x 4 output pixels x all NT 32-channel column tiles, workgroup 2 x 2 waves = 16 x 8 pixels,
-// no LDS, A operand split on the fly, B fragments in split_weights' order) with the input pixel at (stride y + dy, stride x + dx) and the unfold load.
-template <int MODE, int NT>
-__global__ __launch_bounds__(256) void xf_conv_kernel(const XfConv a, const unsigned short* __restrict__ wsplit, const float* __restrict__ inv_ch) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.z;
-  const int x0 = blockIdx.x * 16 + (wave & 1) * 8, y0 = blockIdx.y * 8 + (wave >> 1) * 4;
-  const int i = lane & 31, kh = lane >> 5;
-  const int px = x0 + (i & 7), py = y0 + (i >> 3);
-  const int KS = a.taps * a.cin_pad / 16;
-  f32x16 acc[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
-
-  auto step = [&](const float (&v)[8], int ks) {
-    if constexpr (MODE == 2) {
-      using P = SplitMma<2>;
-      u32x4 ap[2];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        unsigned p[2];
-        P::split(v[2 * e], v[2 * e + 1], P::act_scale(), p);
-        ap[0][e] = p[0]; ap[1][e] = p[1];
-      }
-      const u32x4* wf = (const u32x4*)wsplit;
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        const u32x4 bh = wf[((size_t)(0 * NT + nt) * KS + ks) * 64 + lane], bl = wf[((size_t)(1 * NT + nt) * KS + ks) * 64 + lane];
-        acc[nt] = P::mma(ap[1], bh, acc[nt]);   // smallest cross terms first: l*h, h*l, h*h
-        acc[nt] = P::mma(ap[0], bl, acc[nt]);
-        acc[nt] = P::mma(ap[0], bh, acc[nt]);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float* wrow = a.w32 + ((size_t)ks * 16 + 8 * kh + j) * a.n_pad + (lane & 31);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[nt] = mfma32(v[j], wrow[nt * 32], acc[nt]);
-      }
-    }
-  };
-
-  int ks = 0;
-  if (a.unfold8) {
-    // channel 16 c0 + 8 kh + j = row 2 c0 + kh, column j of the pixel's 8 x 8 block: eight consecutive floats of the plane
-    const bool ok = py < a.H && px < a.W;
-    const float* p = a.in + ((size_t)b * a.in_h + 8 * (ok ? py : 0) + kh) * a.in_w + 8 * (ok ? px : 0);
-    for (int c0 = 0; c0 < 4; ++c0) {
-      float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (ok) {
-        const float4 u0 = *(const float4*)(p + (size_t)2 * c0 * a.in_w), u1 = *(const float4*)(p + (size_t)2 * c0 * a.in_w + 4);
-        v[0] = u0.x; v[1] = u0.y; v[2] = u0.z; v[3] = u0.w; v[4] = u1.x; v[5] = u1.y; v[6] = u1.z; v[7] = u1.w;
-      }
-      step(v, ks++);
-    }
-  } else {
-    for (int tap = 0; tap < a.taps; ++tap) {
-      const int dy = a.taps == 9 ? tap / 3 - 1 : 0, dx = a.taps == 9 ? tap % 3 - 1 : 0;
-      const int yy = py * a.stride + dy, xx = px * a.stride + dx;
-      const bool ok = yy >= 0 && yy < a.in_h && xx >= 0 && xx < a.in_w && py < a.H && px < a.W;
-      const float* p = a.in + (((size_t)b * a.in_h + (ok ? yy : 0)) * a.in_w + (ok ? xx : 0)) * a.cin_pad + 8 * kh;
-      for (int c0 = 0; c0 < a.cin_pad; c0 += 16) {
-        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (ok) {
-          const float4 u0 = *(const float4*)(p + c0), u1 = *(const float4*)(p + c0 + 4);
-          v[0] = u0.x; v[1] = u0.y; v[2] = u0.z; v[3] = u0.w; v[4] = u1.x; v[5] = u1.y; v[6] = u1.z; v[7] = u1.w;
-        }
-        step(v, ks++);
-      }
-    }
-  }
-
-  // epilogue: exact inverse scale of the split, folded BatchNorm bias, ReLU, store
-  float track = 0.f;
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int col = nt * 32 + (lane & 31);
-    const float inv = MODE == 2 ? inv_ch[col] : 1.0f, bias = a.bias[col];
-    const bool col_ok = col < a.out_c;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float v = acc[nt][r] * inv + bias;
-      if (a.relu) v = fmaxf(v, 0.f);
-      const int x = x0 + (r & 3) + 4 * kh, y = y0 + (r >> 2);
-      if (col_ok && x < a.W && y < a.H) {
-        a.out[(((size_t)b * a.H + y) * a.W + x) * a.out_c + col] = v;
-        track = fmaxf(track, fabsf(v));
-      }
-    }
-  }
-  if (MODE == 2) sat_report(a.sat, track);
-}
-
 // one thread per (pixel, four channels)
 __global__ __launch_bounds__(256) void xf_fuse_kernel(const float* __restrict__ x3, const float* __restrict__ x4, const float* __restrict__ x5, float* __restrict__ out,
                                                       int H8, int W8, unsigned* sat) {
@@ -548,32 +452,6 @@ int launch_xf_stem3(const float* in, const XfStem& w, float* out, int batch, int
 int launch_xf_stem4(const float* in, const float* plane, const XfStem& w, float* out, int batch, int H2, int W2, unsigned* sat, hipStream_t s) {
   DIM_REQUIRE(H2 % 2 == 0 && W2 % 4 == 0 && H2 >= 2 && W2 >= 4, "xf_stem4: %dx%d", H2, W2);   // (rows of the full-resolution plane are read as float4)
   hipLaunchKernelGGL(xf_stem4_kernel, dim3(cdiv(W2 / 2, XS_T), cdiv(H2 / 2, XS_T), batch), dim3(256), 0, s, in, plane, w, out, H2, W2, sat);
-  DIM_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_xf_conv(const XfConv& a, bool x3, hipStream_t s) {
-  DIM_REQUIRE(a.in && a.out && a.bias && a.w32 && (!x3 || (a.wx && a.wx->dev && a.wx->mode == 2 && a.wx->n_pad == a.n_pad)), "xf_conv: null operand");
-  DIM_REQUIRE((a.taps == 9 || a.taps == 1) && a.cin_pad % 16 == 0 && a.out_c % 16 == 0 && a.n_pad % 32 == 0 && a.n_pad >= 32 && a.n_pad <= 128 && a.out_c <= a.n_pad,
-              "xf_conv: channels (cin %d, out %d, n_pad %d)", a.cin_pad, a.out_c, a.n_pad);
-  DIM_REQUIRE(a.stride == 1 || (a.stride == 2 && a.taps == 9), "xf_conv: stride %d with %d taps", a.stride, a.taps);
-  DIM_REQUIRE(a.batch >= 1 && a.H >= 1 && a.W >= 1 && a.in_h >= 1 && a.in_w >= 1, "xf_conv: empty map");
-  if (a.unfold8) DIM_REQUIRE(a.taps == 1 && a.cin_pad == 64 && a.in_h == 8 * a.H && a.in_w == 8 * a.W, "xf_conv: unfold of %dx%d into %dx%d", a.in_h, a.in_w, a.H, a.W);
-  else DIM_REQUIRE((a.H - 1) * a.stride < a.in_h && (a.W - 1) * a.stride < a.in_w, "xf_conv: output %dx%d of input %dx%d at stride %d", a.H, a.W, a.in_h, a.in_w, a.stride);
-  const dim3 grid(cdiv(a.W, 16), cdiv(a.H, 8), a.batch);
-  const unsigned short* wsplit = x3 ? a.wx->dev : nullptr;
-  const float* inv = x3 ? a.wx->inv_ch() : nullptr;
-#define XF_CONV(MODE, NT) hipLaunchKernelGGL(HIP_KERNEL_NAME(xf_conv_kernel<MODE, NT>), grid, dim3(256), 0, s, a, wsplit, inv)
-  switch ((x3 ? 10 : 0) + a.n_pad / 32) {
-    case 1: XF_CONV(0, 1); break;
-    case 2: XF_CONV(0, 2); break;
-    case 4: XF_CONV(0, 4); break;
-    case 11: XF_CONV(2, 1); break;
-    case 12: XF_CONV(2, 2); break;
-    case 14: XF_CONV(2, 4); break;
-    default: DIM_REQUIRE(false, "xf_conv: n_pad %d (32, 64 or 128)", a.n_pad);
-  }
-#undef XF_CONV
   DIM_LAUNCH_CHECK();
   return 0;
 }

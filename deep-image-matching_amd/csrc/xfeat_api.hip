@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/dim_hip.h"
+#include "nhwc_conv.h"
 #include "sp_kernels.h"
 #include "xfeat_kernels.h"
 
@@ -27,12 +28,6 @@ const XfGeo XF_BASIC[XF_NB] = {
     {64, 64, 1, 1}, {64, 64, 1, 1}, {64, 64, 1, 1},                               // keypoint_head.0 / .1 / .2
 };
 enum { XF_L_BLOCK2 = 4, XF_L_BLOCK3 = 6, XF_L_BLOCK4 = 9, XF_L_BLOCK5 = 12, XF_L_FUSION = 16, XF_L_HEAT = 18, XF_L_KP = 20 };
-
-// one trunk layer in kernel layout: the [K][N] operand split for the matrix cores and as fp32 [K][n_pad], bias [n_pad]
-struct XfLayer {
-  SplitWeights wx; float* w32 = nullptr; float* bias = nullptr;
-  int cin_pad = 16, taps = 9, stride = 1, n_pad = 32, out_c = 16, relu = 1;
-};
 
 // byte offsets of dim_op_xfeat_select's workspace
 struct XfSelectWs { size_t key, rowcount, rowoff, ncand, cand_score, cand_idx, keys, total; };
@@ -67,7 +62,7 @@ struct dim_xfeat {
   dim_xfeat_config cfg;
   int max_batch, max_h, max_w, capacity, stride;
   XfStem stem;
-  XfLayer L[XF_NB], fusion2;   // L[0..3] unused (stem); fusion2 = block_fusion.2 (1x1 with bias, no activation)
+  NhwcConvLayer L[XF_NB], fusion2;   // L[0..3] unused (stem); fusion2 = block_fusion.2 (1x1 with bias, no activation)
   float *heat_w, *heat_b, *kp_w, *kp_b;
   float *norm, *a2, *b2, *q0, *q1, *q2, *e[5], *f[3], *g[3], *g3, *h1, *k1h, *key;
   double *partial, *stats;
@@ -140,24 +135,12 @@ int dim_xfeat_create(const dim_xfeat_weights* w, const dim_xfeat_config* cfg, in
     h->stem = XfStem{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9]};
   }
   // trunk: [K = taps * cin_pad][N] operands
-  auto upload = [&](XfLayer& L, const float* wt, int co, int ci, int k, int strd, const std::vector<double>* scale, const std::vector<float>& bias, int relu) -> int {
-    L.taps = k * k; L.stride = strd; L.relu = relu; L.cin_pad = xf_pad16(ci); L.n_pad = xf_pad32(co); L.out_c = xf_pad16(co);
+  auto upload = [&](NhwcConvLayer& L, const float* wt, int co, int ci, int k, int strd, const std::vector<double>* scale, const std::vector<float>& bias, int relu) -> int {
+    L.taps = k * k; L.stride = strd; L.relu = relu; L.cin_pad = dim_pad16(ci);
     const int K = L.taps * L.cin_pad;
     std::vector<float> kn((size_t)K * co, 0.0f);
-    for (int a = 0; a < co; ++a)
-      for (int b = 0; b < ci; ++b)
-        for (int t = 0; t < L.taps; ++t) {
-          const float v = wt[((size_t)a * ci + b) * L.taps + t];
-          kn[((size_t)t * L.cin_pad + b) * co + a] = scale ? (float)((double)v * (*scale)[a]) : v;
-        }
-    DIM_TRY(dim_upload_gemm_split(hb, &L.wx, kn.data(), K, co, L.n_pad, 2));
-    std::vector<float> w32((size_t)K * L.n_pad, 0.0f), bb(L.n_pad, 0.0f);
-    for (int kk = 0; kk < K; ++kk)
-      for (int n = 0; n < co; ++n) w32[(size_t)kk * L.n_pad + n] = kn[(size_t)kk * co + n];
-    for (int n = 0; n < co; ++n) bb[n] = bias[n];
-    DIM_TRY(dim_upload_f32(hb, &L.w32, w32));
-    DIM_TRY(dim_upload_f32(hb, &L.bias, bb));
-    return 0;
+    nhwc_conv_pack_oihw(kn, co, 0, wt, co, ci, k, L.cin_pad, scale);
+    return nhwc_conv_upload(hb, &L, kn, K, co, bias);
   };
   for (int i = XF_L_BLOCK2; i < XF_NB; ++i) {
     const XfGeo& g = XF_BASIC[i];
@@ -200,56 +183,54 @@ int dim_xfeat_extract(dim_xfeat* h, const float* images_dev, int batch, int H, i
   const int H2 = Hr / 2, W2 = Wr / 2, H4 = Hr / 4, W4 = Wr / 4, H8 = Hr / 8, W8 = Wr / 8, H16 = Hr / 16, W16 = Wr / 16, H32 = Hr / 32, W32 = Wr / 32;
   const bool x3 = dim_precision_mode() == 2;   // fp16x3 on the matrix cores; every other mode runs the fp32 MFMA form
   unsigned* const sat = x3 ? dim_sat_counter(DIM_SAT_XFEAT) : nullptr;
-#define XF_RUN(x) do { int rc__ = (x); if (rc__ != 0) return rc__; } while (0)
-  auto conv = [&](const XfLayer& L, const float* in, int in_h, int in_w, float* out, int Ho, int Wo, bool unfold) -> int {
-    XfConv a;
+  auto conv = [&](const NhwcConvLayer& L, const float* in, int in_h, int in_w, float* out, int Ho, int Wo, bool unfold) -> int {
+    NhwcConv a;
     a.in = in; a.cin_pad = L.cin_pad; a.taps = L.taps; a.stride = L.stride; a.in_h = in_h; a.in_w = in_w; a.unfold8 = unfold ? 1 : 0;
     a.wx = &L.wx; a.w32 = L.w32; a.bias = L.bias; a.n_pad = L.n_pad; a.out = out; a.out_c = L.out_c; a.relu = L.relu;
     a.batch = batch; a.H = Ho; a.W = Wo; a.sat = sat;
-    return launch_xf_conv(a, x3, s);
+    return launch_nhwc_conv(a, x3, s);
   };
   // preparation: resize + channel mean, fp64 statistics in two fixed-order stages, InstanceNorm (XFM:219-240, XFN:135-136)
   const int nblk = xf_prep_blocks(Hr, Wr);
-  XF_RUN(launch_xf_gray(images_dev, channels, H, W, h->norm, h->partial, batch, Hr, Wr, s));
-  XF_RUN(launch_xf_stats(h->partial, nblk, Hr * Wr, h->stats, batch, s));
-  XF_RUN(launch_xf_normalize(h->norm, h->stats, batch, Hr * Wr, sat, s));
+  DIM_RUN(launch_xf_gray(images_dev, channels, H, W, h->norm, h->partial, batch, Hr, Wr, s));
+  DIM_RUN(launch_xf_stats(h->partial, nblk, Hr * Wr, h->stats, batch, s));
+  DIM_RUN(launch_xf_normalize(h->norm, h->stats, batch, Hr * Wr, sat, s));
   // stem: block1 + skip1 (XFN:139-140)
-  XF_RUN(launch_xf_stem12(h->norm, h->stem, h->a2, batch, Hr, Wr, s));
-  XF_RUN(launch_xf_stem3(h->a2, h->stem, h->b2, batch, H2, W2, s));
-  XF_RUN(launch_xf_stem4(h->b2, h->norm, h->stem, h->q0, batch, H2, W2, sat, s));
+  DIM_RUN(launch_xf_stem12(h->norm, h->stem, h->a2, batch, Hr, Wr, s));
+  DIM_RUN(launch_xf_stem3(h->a2, h->stem, h->b2, batch, H2, W2, s));
+  DIM_RUN(launch_xf_stem4(h->b2, h->norm, h->stem, h->q0, batch, H2, W2, sat, s));
   // trunk (XFN:140-143)
-  XF_RUN(conv(h->L[XF_L_BLOCK2], h->q0, H4, W4, h->q1, H4, W4, false));
-  XF_RUN(conv(h->L[XF_L_BLOCK2 + 1], h->q1, H4, W4, h->q2, H4, W4, false));
-  XF_RUN(conv(h->L[XF_L_BLOCK3], h->q2, H4, W4, h->e[0], H8, W8, false));
-  XF_RUN(conv(h->L[XF_L_BLOCK3 + 1], h->e[0], H8, W8, h->e[1], H8, W8, false));
-  XF_RUN(conv(h->L[XF_L_BLOCK3 + 2], h->e[1], H8, W8, h->e[2], H8, W8, false));      // x3
-  XF_RUN(conv(h->L[XF_L_BLOCK4], h->e[2], H8, W8, h->f[0], H16, W16, false));
-  XF_RUN(conv(h->L[XF_L_BLOCK4 + 1], h->f[0], H16, W16, h->f[1], H16, W16, false));
-  XF_RUN(conv(h->L[XF_L_BLOCK4 + 2], h->f[1], H16, W16, h->f[2], H16, W16, false));  // x4
-  XF_RUN(conv(h->L[XF_L_BLOCK5], h->f[2], H16, W16, h->g[0], H32, W32, false));
-  XF_RUN(conv(h->L[XF_L_BLOCK5 + 1], h->g[0], H32, W32, h->g[1], H32, W32, false));
-  XF_RUN(conv(h->L[XF_L_BLOCK5 + 2], h->g[1], H32, W32, h->g[2], H32, W32, false));
-  XF_RUN(conv(h->L[XF_L_BLOCK5 + 3], h->g[2], H32, W32, h->g3, H32, W32, false));    // x5
+  DIM_RUN(conv(h->L[XF_L_BLOCK2], h->q0, H4, W4, h->q1, H4, W4, false));
+  DIM_RUN(conv(h->L[XF_L_BLOCK2 + 1], h->q1, H4, W4, h->q2, H4, W4, false));
+  DIM_RUN(conv(h->L[XF_L_BLOCK3], h->q2, H4, W4, h->e[0], H8, W8, false));
+  DIM_RUN(conv(h->L[XF_L_BLOCK3 + 1], h->e[0], H8, W8, h->e[1], H8, W8, false));
+  DIM_RUN(conv(h->L[XF_L_BLOCK3 + 2], h->e[1], H8, W8, h->e[2], H8, W8, false));      // x3
+  DIM_RUN(conv(h->L[XF_L_BLOCK4], h->e[2], H8, W8, h->f[0], H16, W16, false));
+  DIM_RUN(conv(h->L[XF_L_BLOCK4 + 1], h->f[0], H16, W16, h->f[1], H16, W16, false));
+  DIM_RUN(conv(h->L[XF_L_BLOCK4 + 2], h->f[1], H16, W16, h->f[2], H16, W16, false));  // x4
+  DIM_RUN(conv(h->L[XF_L_BLOCK5], h->f[2], H16, W16, h->g[0], H32, W32, false));
+  DIM_RUN(conv(h->L[XF_L_BLOCK5 + 1], h->g[0], H32, W32, h->g[1], H32, W32, false));
+  DIM_RUN(conv(h->L[XF_L_BLOCK5 + 2], h->g[1], H32, W32, h->g[2], H32, W32, false));
+  DIM_RUN(conv(h->L[XF_L_BLOCK5 + 3], h->g[2], H32, W32, h->g3, H32, W32, false));    // x5
   // pyramid fusion (XFN:146-148): the sum is formed by a small kernel of its own (a 64-channel map at 1/8 resolution: 1.5 % of the stem's traffic),
   // not inside block_fusion.0's operand load, where every one of the nine taps would repeat the two bilinear blends
-  XF_RUN(launch_xf_fuse(h->e[2], h->f[2], h->g3, h->e[0], batch, H8, W8, sat, s));
-  XF_RUN(conv(h->L[XF_L_FUSION], h->e[0], H8, W8, h->e[1], H8, W8, false));
-  XF_RUN(conv(h->L[XF_L_FUSION + 1], h->e[1], H8, W8, h->e[0], H8, W8, false));
-  XF_RUN(conv(h->fusion2, h->e[0], H8, W8, h->e[3], H8, W8, false));                 // feats
+  DIM_RUN(launch_xf_fuse(h->e[2], h->f[2], h->g3, h->e[0], batch, H8, W8, sat, s));
+  DIM_RUN(conv(h->L[XF_L_FUSION], h->e[0], H8, W8, h->e[1], H8, W8, false));
+  DIM_RUN(conv(h->L[XF_L_FUSION + 1], h->e[1], H8, W8, h->e[0], H8, W8, false));
+  DIM_RUN(conv(h->fusion2, h->e[0], H8, W8, h->e[3], H8, W8, false));                 // feats
   // reliability head (XFN:79-84) and the dense descriptors' normalisation (XFM:70)
-  XF_RUN(conv(h->L[XF_L_HEAT], h->e[3], H8, W8, h->e[0], H8, W8, false));
-  XF_RUN(conv(h->L[XF_L_HEAT + 1], h->e[0], H8, W8, h->e[1], H8, W8, false));
-  XF_RUN(launch_xf_dense_tail(h->e[1], h->heat_w, h->heat_b, h->e[3], h->h1, h->e[4], batch * H8 * W8, s));
+  DIM_RUN(conv(h->L[XF_L_HEAT], h->e[3], H8, W8, h->e[0], H8, W8, false));
+  DIM_RUN(conv(h->L[XF_L_HEAT + 1], h->e[0], H8, W8, h->e[1], H8, W8, false));
+  DIM_RUN(launch_xf_dense_tail(h->e[1], h->heat_w, h->heat_b, h->e[3], h->h1, h->e[4], batch * H8 * W8, s));
   // keypoint head on the 8 x 8 unfolding of the normalised image (XFN:87-92,152), softmax + depth-to-space (XFM:242-247)
-  XF_RUN(conv(h->L[XF_L_KP], h->norm, Hr, Wr, h->e[0], H8, W8, true));
-  XF_RUN(conv(h->L[XF_L_KP + 1], h->e[0], H8, W8, h->e[1], H8, W8, false));
-  XF_RUN(conv(h->L[XF_L_KP + 2], h->e[1], H8, W8, h->e[0], H8, W8, false));
-  XF_RUN(launch_xf_kp_tail(h->e[0], h->kp_w, h->kp_b, h->k1h, batch, H8, W8, s));
+  DIM_RUN(conv(h->L[XF_L_KP], h->norm, Hr, Wr, h->e[0], H8, W8, true));
+  DIM_RUN(conv(h->L[XF_L_KP + 1], h->e[0], H8, W8, h->e[1], H8, W8, false));
+  DIM_RUN(conv(h->L[XF_L_KP + 2], h->e[1], H8, W8, h->e[0], H8, W8, false));
+  DIM_RUN(launch_xf_kp_tail(h->e[0], h->kp_w, h->kp_b, h->k1h, batch, H8, W8, s));
   // selection (XFM:74-87) and the sparse tail (XFM:90-96)
-  XF_RUN(xf_select_chain(h->k1h, h->h1, h->key, h->cfg.detection_threshold, h->cfg.top_k, h->capacity, batch, Hr, Wr, h->rowcount, h->rowoff, h->ncand, h->cand_score,
+  DIM_RUN(xf_select_chain(h->k1h, h->h1, h->key, h->cfg.detection_threshold, h->cfg.top_k, h->capacity, batch, Hr, Wr, h->rowcount, h->rowoff, h->ncand, h->cand_score,
                          h->cand_idx, h->topk_keys, h->kpts_px, scores_dev, (int*)n_kpts_dev, s));
-  XF_RUN(launch_xf_sparse(h->e[4], h->kpts_px, (const int*)n_kpts_dev, desc_dev, kpts_xy_dev, h->stride, h->capacity, batch, Hr, Wr, rw, rh, s));
-#undef XF_RUN
+  DIM_RUN(launch_xf_sparse(h->e[4], h->kpts_px, (const int*)n_kpts_dev, desc_dev, kpts_xy_dev, h->stride, h->capacity, batch, Hr, Wr, rw, rh, s));
   h->last_h = Hr; h->last_w = Wr;
   return 0;
 }

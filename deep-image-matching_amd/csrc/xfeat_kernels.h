@@ -3,9 +3,6 @@
 #pragma once
 #include "dim_kernels.h"
 
-inline int xf_pad16(int c) { return (c + 15) / 16 * 16; }
-inline int xf_pad32(int c) { return (c + 31) / 32 * 32; }
-
 // ---- preparation (XFM:219-240, XFN:135-136) ----
 // gray[b][y][x] = mean over channels of the bilinear resize (align_corners=False, no antialias) of image [b][in_h][in_w][C] to H x W, and per
 // (image, workgroup) the fp64 pair (sum, sum of squares) of what it wrote: partial [b][xf_prep_blocks(H, W)][2]
@@ -37,22 +34,7 @@ int launch_xf_stem3(const float* in, const XfStem& w, float* out, int batch, int
 // (channels 24..31 zero); `sat`: range guard of block2's input
 int launch_xf_stem4(const float* in, const float* plane, const XfStem& w, float* out, int batch, int H2, int W2, unsigned* sat, hipStream_t s);
 
-// ---- trunk: implicit GEMM on the matrix cores, alike.hip's ak_conv_kernel conventions (NHWC, channels padded to 16, split_weights fragment order,
-// exact inverse scale in the epilogue) with a stride and the unfold operand load ----
-//   out[b][y][x][co] = act( sum_{tap,ci} in[b][stride y + dy][stride x + dx][ci] w[tap * cin_pad + ci][co] + bias[co] ), zero padding, taps = 9 | 1
-// unfold8: `in` is the image plane [b][8 H][8 W] read as its 64-channel 8 x 8 unfolding, channel = 8 dy + dx (XFN:113-120); taps = 1, cin_pad = 64
-struct XfConv {
-  const float* in = nullptr; int cin_pad = 16, taps = 9, stride = 1, in_h = 0, in_w = 0, unfold8 = 0;
-  const SplitWeights* wx = nullptr;   // fp16x3: split_weights(K, N, n_pad, 2) of the [K][N] operand
-  const float* w32 = nullptr;         // fp32 MFMA: the same operand [K][n_pad]
-  const float* bias = nullptr;        // [n_pad]
-  int n_pad = 32;
-  float* out = nullptr; int out_c = 16;
-  int relu = 1;
-  int batch = 1, H = 0, W = 0;        // output size
-  unsigned* sat = nullptr;            // fp16x3 range guard of the stored activations
-};
-int launch_xf_conv(const XfConv& a, bool x3, hipStream_t s);
+// ---- trunk: launch_nhwc_conv (nhwc_conv.h) ----
 // out = x3 + up(x4) + up(x5), bilinear with align_corners=False (XFN:146-148); 64 channels; `sat`: range guard of block_fusion's input
 int launch_xf_fuse(const float* x3, const float* x4, const float* x5, float* out, int batch, int H8, int W8, unsigned* sat, hipStream_t s);
 

@@ -94,7 +94,7 @@ class XFeatHIP(capi.ResidentHandle):
         return kp, sc, de, n
 
     def extract_batch_guarded(self, images: torch.Tensor, logger=None):
-        """extract_batch under the fp16x3 range guard (capi.run_guarded): the trunk runs as fp16 splits on the matrix cores (xfeat.hip), exact for
+        """extract_batch under the fp16x3 range guard (capi.run_guarded): the trunk runs as fp16 splits on the matrix cores (nhwc_conv.hip), exact for
         |activation| <= 4094; a call that leaves that range is repeated on the fp32 MFMA path.  Synchronises."""
         return self.guarded(lambda: self.extract_batch(images), "XFeat", logger)
 

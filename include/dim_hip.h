@@ -537,6 +537,23 @@ int dim_convx6_create(const float* w_oihw_host, int cin, int cout, void** out_ha
 int dim_op_conv3x3_x6_nhwc_f32(const float* in, const void* w_x6_handle, const float* bias, float* out, int batch, int H, int W,
                                int cin, int cout, int pool2x2, int relu, void* stream);
 
+/* The implicit-GEMM NHWC convolution of ALIKE's encoder and XFeat's trunk (csrc/nhwc_conv.hip) as one layer:
+ *   out[b][y][x][co] = act( sum_{tap,ci} in[b][stride y + dy][stride x + dx][ci] w[co][ci][tap] + sum_ci in2[b][y][x][ci] w2[co][ci] + bias[co] )
+ * dim_nhwc_conv_create takes the reference's OIHW fp32 weight (cout <= 128, kernel 3 with zero padding 1 or kernel 1, stride 1 | 2), optionally the
+ * 1x1 OIHW weight w2 of a second input with cin2 channels at output resolution (NULL / 0: none), bias [cout] and relu; free with dim_nhwc_conv_destroy.
+ * All maps are NHWC fp32 with channel strides padded up to multiples of 16: in [batch][in_h][in_w][pad16(cin)], in2 [batch][H][W][pad16(cin2)], out
+ * [batch][H][W][pad16(cout)]; padding channels of the inputs must hold zeros and those of the outputs are written as zeros.  Input positions outside
+ * in_h x in_w read as zero.  img3 (cin = 3): in is the [batch][in_h][in_w][3] image, which may be smaller than the H x W frame.  unfold8 (cin = 64,
+ * kernel 1): in is the plane [batch][8 H][8 W] read as its 8 x 8 unfolding, channel = 8 dy + dx.  pool = 2 | 4 (H, W multiples of it): the max-pooled
+ * copy of the activated map goes to pooled [batch][H/pool][W/pool][pad16(cout)] as well; 0: none.  stride 2, unfold8 and img3 exclude each other, and
+ * the first two exclude in2 and pool, img3 excludes in2.  Arithmetic: fp16x3 when dim_tune_set key 1 is 2 (DIM_SAT_OP counts stored |values| > 4094), fp32 MFMA otherwise. */
+typedef struct dim_nhwc_conv dim_nhwc_conv;
+int dim_nhwc_conv_create(const float* w_oihw, int cout, int cin, int ksize, int stride, const float* w2_oihw, int cin2, const float* bias, int relu,
+                         dim_nhwc_conv** out);
+void dim_nhwc_conv_destroy(dim_nhwc_conv* h);
+int dim_op_nhwc_conv_f32(const dim_nhwc_conv* h, const float* in, int in_h, int in_w, int img3, int unfold8, const float* in2, float* out, float* pooled,
+                         int pool, int batch, int H, int W, void* stream);
+
 /* conv1a: [batch][H][W] -> [batch][H][W][64], weights [9][64], bias, ReLU. */
 int dim_op_conv1a_f32(const float* in, const float* w_tap_cout, const float* bias, float* out, int batch, int H, int W,
                       void* stream);

@@ -287,6 +287,88 @@ def conv1a_case(lib, batch, H, W, device="cpu", runs=1):
     return _dense_result(bufs, (batch, H, W, 64), ref, None)
 
 
+# ---------------------------------------------------------------------------------------------------------------- NHWC implicit-GEMM convolution
+# name: (kernel, cin, cin2, N, stride, (in_h, in_w), (H, W), pool, relu, form); a workgroup covers 16 x 8 output pixels, so every case has a partial tile
+# and A, B, C, E full ones as well; N = 16 / 8, 48, 96, 128 -> 1, 2, 3, 4 column tiles
+NHWC_CONV_CASES = {
+    "A": (3, 16, 0, 16, 1, (9, 17), (9, 17), 0, 1, ""),
+    "B": (3, 3, 0, 8, 1, (13, 19), (32, 32), 2, 1, "img3"),        # the image is smaller than the frame: what lies past it is zero padding
+    "C": (3, 32, 16, 48, 1, (12, 20), (12, 20), 4, 1, ""),
+    "D": (1, 48, 0, 96, 1, (5, 7), (5, 7), 0, 0, ""),
+    "E": (3, 32, 0, 128, 2, (11, 23), (6, 12), 0, 1, ""),
+    "F": (1, 64, 0, 64, 1, (24, 40), (3, 5), 0, 1, "unfold8"),     # the plane read as its 8 x 8 unfolding
+}
+
+
+def _nhwc_pad16(t):
+    """[b][c][h][w] -> NHWC with the channel stride padded up to a multiple of 16 (zeros)."""
+    t = t.permute(0, 2, 3, 1)
+    return F.pad(t, (0, -t.shape[3] % 16)).contiguous()
+
+
+@functools.lru_cache(maxsize=None)
+def _nhwc_conv_inputs(name, batch):
+    k, cin, cin2, N, stride, (ih, iw), (H, W), pool, relu, form = NHWC_CONV_CASES[name]
+    g = torch.Generator().manual_seed(ord(name))
+    w = (torch.randn(N, cin, k, k, generator=g) * 0.1).contiguous()
+    b = torch.randn(N, generator=g)
+    if form == "unfold8":
+        plane = torch.randn(batch, 1, ih, iw, generator=g)
+        x = F.unfold(plane, 8, stride=8).view(batch, 64, H, W)
+        xin = plane[:, 0].contiguous()
+    else:
+        x = torch.randn(batch, cin, ih, iw, generator=g)
+        xin = x.permute(0, 2, 3, 1).contiguous() if form == "img3" else _nhwc_pad16(x)
+        if form == "img3":
+            x = F.pad(x, (0, W - iw, 0, H - ih))
+    pre = F.conv2d(x.double(), w.double(), b.double(), stride=stride, padding=k // 2)
+    mag = F.conv2d(x.abs().double(), w.abs().double(), stride=stride, padding=k // 2)
+    w2 = x2in = None
+    if cin2:
+        x2 = torch.randn(batch, cin2, H, W, generator=g)
+        w2 = (torch.randn(N, cin2, 1, 1, generator=g) * 0.1).contiguous()
+        pre = pre + F.conv2d(x2.double(), w2.double())
+        mag = mag + F.conv2d(x2.abs().double(), w2.abs().double())
+        x2in = _nhwc_pad16(x2)
+    assert pre.shape == (batch, N, H, W), pre.shape
+    ref = torch.relu(pre) if relu else pre
+    ref_pool = _nhwc_pad16(F.max_pool2d(ref, pool)) if pool else None
+    return xin, x2in, w, w2, b, _nhwc_pad16(ref), ref_pool, torch.tensor(mag.max().item(), dtype=torch.float64)
+
+
+def nhwc_conv_case(lib, name, batch=2, device="cpu", runs=1):
+    """One case of NHWC_CONV_CASES through dim_nhwc_conv_create + dim_op_nhwc_conv_f32 (nhwc_conv_kernel<MODE, NT> in the arithmetic form that is active at
+    the call) vs fp64 conv2d (+ the 1x1 product of in2) / relu / max_pool2d on the zero-padded frame (img3) or on F.unfold's channels (unfold8).
+    -> (out, pooled or None, N): two OpResults whose references carry the padding channels [N, pad16(N)) as zeros; scale = max of conv(|x|, |w|)."""
+    k, cin, cin2, N, stride, (ih, iw), (H, W), pool, relu, form = NHWC_CONV_CASES[name]
+    xin, x2in, w, w2, b, ref, ref_pool, mag = _nhwc_conv_inputs(name, batch)
+    out_c = ref.shape[3]
+    xd = xin.to(device)
+    x2d = x2in.to(device) if x2in is not None else None
+    handle = ctypes.c_void_p()
+    assert lib.dim_nhwc_conv_create(p(w), N, cin, k, stride, p(w2), cin2, p(b), relu, ctypes.byref(handle)) == 0, lib.dim_last_error()
+    outs, pools = [], []
+    try:
+        for _ in range(runs):
+            out = _dense_out(batch * H * W * out_c, device)
+            pooled = _dense_out(batch * (H // pool) * (W // pool) * out_c, device) if pool else None
+            rc = lib.dim_op_nhwc_conv_f32(handle, p(xd), ih, iw, int(form == "img3"), int(form == "unfold8"), p(x2d), p(out), p(pooled), pool, batch, H, W, None)
+            assert rc == 0, lib.dim_last_error()
+            _sync(device)
+            outs.append(out)
+            pools.append(pooled)
+    finally:
+        lib.dim_nhwc_conv_destroy(handle)
+    r_pool = _dense_result(pools, (batch, H // pool, W // pool, out_c), ref_pool, mag) if pool else None
+    return _dense_result(outs, (batch, H, W, out_c), ref, mag), r_pool, N
+
+
+def nhwc_conv_figure(r, x3):
+    """(figure, bound) of one result: fp16x3 rel_err < 4e-7, fp32 max abs error < 1e-4 — the bounds of the 3 x 3 convolution tests on the same input
+    distribution (x ~ randn, w ~ 0.1 randn, b ~ randn); every K here is below their 1152."""
+    return (r.rel_err, 4e-7) if x3 else (r.abs_err.max().item(), 1e-4)
+
+
 # ---------------------------------------------------------------------------------------------------------------- LightGlue feed-forward
 def _ffn_ln_gelu_case(lib, M, K, seed, device="cpu"):
     """gelu(layer_norm(A W + b)) through dim_op_gemm_x6_ln_gelu_f32 -> (device result, fp64 reference)."""

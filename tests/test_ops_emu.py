@@ -122,6 +122,24 @@ def test_conv3x3_split_precision_is_fp32_accurate(emu_lib, split_mode, cin, cout
     assert r.rel_err < 4e-7 and r.guard_ok
 
 
+@pytest.mark.parametrize("mode", [2, 0], ids=["fp16x3", "fp32"])
+@pytest.mark.parametrize("name", sorted(op_cases.NHWC_CONV_CASES))
+def test_nhwc_conv_vs_fp64(emu_lib, name, mode):
+    """nhwc_conv_kernel<MODE, NT> (ALIKE's encoder / XFeat's trunk) through dim_nhwc_conv_create + dim_op_nhwc_conv_f32: every operand form, both pools,
+    1 .. 4 column tiles, full and partial 16 x 8 tiles, in both arithmetic forms (dim_tune_set key 1)."""
+    try:
+        emu_lib.dim_tune_set(1, mode)
+        r_out, r_pool, N = op_cases.nhwc_conv_case(emu_lib, name)
+    finally:
+        emu_lib.dim_tune_set(1, 2)
+    for r in (r_out, r_pool) if r_pool is not None else (r_out,):
+        figure, bound = op_cases.nhwc_conv_figure(r, mode == 2)
+        print(f"nhwc_conv {name} mode {mode}: figure {figure:.4g} bound {bound:.4g}")
+        assert r.guard_ok
+        assert bool((r.out[..., N:] == 0.0).all()), "a padding channel is not exactly zero"
+        assert figure < bound
+
+
 @pytest.mark.parametrize("regime", ["tiny", "large", "overflow"])
 def test_fp16x3_range_behaviour(emu_lib, regime):
     """fp16x3's narrow exponent: activations are scaled by 16 and clamped to +-65504 before the split.

@@ -11,7 +11,7 @@ recorded case: test_lightglue_gpu.test_ffn_layernorm_gelu_fused_op_at_production
 every case runs TWICE on the same inputs and must give the same bits, stay within the bound the emulator test asserts for the operator, and leave the
 guard band around its output (op_cases.py) untouched.
 
-Case -> kernel (from launch_gemm / launch_gemm_x6 / launch_gemm_x6_nt / launch_conv3x3 / launch_conv3x3_x6 / launch_conv1a / launch_nms; wg = workgroups):
+Case -> kernel (from launch_gemm / launch_gemm_x6 / launch_gemm_x6_nt / launch_conv3x3 / launch_conv3x3_x6 / launch_conv1a / launch_nhwc_conv / launch_nms; wg = workgroups):
 
   test_gemm_f32                (200,65,64) (130,256,256) (1,4,32)           gemm_mfma_kernel<0>          4 / 4 / 1 wg
                                (150,140,64) b_is_nk                         gemm_mfma_kernel<1>          4 wg
@@ -36,6 +36,11 @@ Case -> kernel (from launch_gemm / launch_gemm_x6 / launch_gemm_x6_nt / launch_c
   test_conv3x3_x6_fp16x3       the same seven shapes                        conv3x3_x6_kernel<cin,pool,1,false,2,false,false>
   test_conv3x3_x6_bf16x6       the same seven shapes, key 2 = 0 / 1 / 2     conv3x3_x6_kernel<cin,pool,0 / 1 / 2,false,1,false,false>
   test_conv1a                  (2,45,70) / (2,130,150)                      conv1a_kernel                180 / 780 wg
+  test_nhwc_conv               batch 2, key 1 = 2 / 0 -> MODE 2 (fp16x3) / 0 (fp32); op_cases.NHWC_CONV_CASES:
+                               A 3x3 16 -> 16 9x17, B 3x3 img3 13x19 in a 32x32 frame -> 8 pool 2     nhwc_conv_kernel<MODE,1>     8 / 16 wg
+                               C 3x3 32 (+ in2 16) -> 48 12x20 pool 4, F 1x1 unfold8 24x40 -> 64 3x5  nhwc_conv_kernel<MODE,2>     8 / 2 wg
+                               D 1x1 48 -> 96 5x7 no ReLU                                              nhwc_conv_kernel<MODE,3>     2 wg
+                               E 3x3 stride 2 32 -> 128 11x23 -> 6x12                                  nhwc_conv_kernel<MODE,4>     2 wg
   test_nms_small_maps          radius 0: nms_kernel<0,32,512,8>; 2: <2,32,..>; 5, 6: <5|6,16,512,8>; radius 1, 3, 4: key 7 = 0 nms_kernel<r,32,512,8>,
                                key 7 = 2 nms_kernel<1,64,1024,8> / <3,64,1024,10> / <4,64,1024,12>
   test_nms_large_map           4 x 500 x 500, 8 * 8 * 4 = 256 tiles: the 64-tile kernels by themselves under key 7 = 1, the 32-tile ones under key 7 = 0
@@ -189,6 +194,15 @@ def test_conv1a(hip_lib, batch, H, W):
     """1e-5 absolute: derived in test_ops_emu.test_conv1a_vs_fp64 (nine fmas and a bias on an image in [0, 1], weights of order 0.3)."""
     r = op_cases.conv1a_case(hip_lib, batch, H, W, device=DEV, runs=2)
     check(r, r.abs_err.max().item(), 1e-5)
+
+
+@pytest.mark.parametrize("name,mode", [(n, m) for n in sorted(op_cases.NHWC_CONV_CASES) for m in (2, 0)])
+def test_nhwc_conv(hip_lib, name, mode):
+    with tuned(hip_lib, {1: mode}):
+        r_out, r_pool, N = op_cases.nhwc_conv_case(hip_lib, name, device=DEV, runs=2)
+    for r in (r_out, r_pool) if r_pool is not None else (r_out,):
+        check(r, *op_cases.nhwc_conv_figure(r, mode == 2))
+        assert bool((r.out[..., N:] == 0.0).all()), "a padding channel is not exactly zero"
 
 
 # ---------------------------------------------------------------------------------------------------------------- simple_nms
