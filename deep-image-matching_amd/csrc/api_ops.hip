@@ -128,6 +128,12 @@ int dim_gemm_probe() { return g_gemm_probe; }
 static int g_attn_probe = 0;
 int dim_attn_probe() { return g_attn_probe; }
 #endif
+#ifdef DIM_RESEARCH   // the research build keeps the dense descriptor head
+int dim_sparse_desc() { return 0; }
+#else
+static int g_sparse_desc = 1;
+int dim_sparse_desc() { return tuned(20, g_sparse_desc); }
+#endif
 static int g_al_tile_rows = 16;
 int dim_aliked_tile_rows() { return tuned(10, g_al_tile_rows); }
 static int g_al_fuse_bn = 1;
@@ -397,6 +403,9 @@ int dim_tune_set(int key, int value) {
   if (key == 16) g_fuse_sp_head = value;
   if (key == 17) g_defer_assign = value;
   if (key == 18) g_follow_stop = value;
+#ifndef DIM_RESEARCH
+  if (key == 20) g_sparse_desc = value;
+#endif
 #ifdef DIM_RESEARCH
   if (key == 12) g_attn_probe = value;
   if (key == 13) g_gemm_probe = value;
@@ -406,15 +415,15 @@ int dim_tune_set(int key, int value) {
   DIM_REQUIRE(key < 12 || key > 15, "dim_tune_set: key %d selects a research prototype / timing probe that the product library does not contain "
               "(build.build_variant(\"research\", [\"-DDIM_RESEARCH\"]) -> libdim_hip_research.so)", key);
 #endif
-  DIM_REQUIRE(key >= 0 && key <= 18, "dim_tune_set: unknown key %d", key);
+  DIM_REQUIRE((key >= 0 && key <= 18) || key == 20, "dim_tune_set: unknown key %d", key);
   return 0;
 }
 
 int dim_handle_tune_set(void* handle, int key, int value) {
   DimHandleBase* b = (DimHandleBase*)handle;
   DIM_REQUIRE(b != nullptr && b->magic == DIM_HANDLE_MAGIC, "dim_handle_tune_set: not an extractor / matcher handle of this library");
-  DIM_REQUIRE(key == 1 || key == 3 || key == 4 || key == 5 || key == 8 || key == 9 || key == 10 || key == 11 || key == 16 || key == 17 || key == 18,
-              "dim_handle_tune_set: key %d has no per-handle form (arithmetic 1; fusion 3, 4, 5, 8, 9, 11, 16, 17, 18; ALIKED tile rows 10)", key);
+  DIM_REQUIRE(key == 1 || key == 3 || key == 4 || key == 5 || key == 8 || key == 9 || key == 10 || key == 11 || key == 16 || key == 17 || key == 18 || key == 20,
+              "dim_handle_tune_set: key %d has no per-handle form (arithmetic 1; fusion 3, 4, 5, 8, 9, 11, 16, 17, 18, 20; ALIKED tile rows 10)", key);
   b->tune.v[key] = value < 0 ? -1 : value;
   return 0;
 }

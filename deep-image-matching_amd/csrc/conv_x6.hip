@@ -381,6 +381,97 @@ __global__ __launch_bounds__(256, ((PF == 2 || MR == 4) ? 2 : 3)) void conv3x3_x
   else run_epilogue(std::true_type{});
 }
 
+// The fp16x3 convolution on LISTED pixels (SuperPoint's descriptor head on the cells that keypoints sample): the M rows of the implicit GEMM are
+// the pixels cell_rows[b][0 .. n_rows[b]) of a pre-split (PIN) input, the output is compact: out[b][row][COUT] fp32.  Workgroup = 128 rows x all
+// COUT channels, wave w owns rows 32 w .. 32 w + 31 x COUT / 32 accumulators.  A lane reads its A operands (8 consecutive channels of one plane
+// of one tap = 16 bytes) straight from the input planes — a gathered row has no halo to share, so there is no LDS image of the input; the weight
+// slices of all COUT / 64 channel blocks of one (chunk, kernel row) travel to LDS by LDS-DMA.  Per row the arithmetic is conv3x3_x6_kernel's:
+// K order chunk, kernel row, tap; the cross terms of SplitMma<2> smallest first; epilogue acc * inv + bias, ReLU, range guard.  MFMA rows are
+// independent, so row r equals the dense kernel's output at pixel cell_rows[b][r] bit for bit.  Taps outside the image read as zero; workgroups
+// past n_rows[b] exit at once (the grid covers `slots` rows, the host never reads the count).
+template <int CIN, int COUT>
+__global__ __launch_bounds__(256, 2) void conv3x3_x6_rows_kernel(const unsigned short* __restrict__ in, const unsigned short* __restrict__ wx,
+                                                                 const float* __restrict__ bias, float* __restrict__ out, int H, int W, int relu,
+                                                                 const float* __restrict__ inv_ch, unsigned* sat, const int* __restrict__ cell_rows,
+                                                                 const int* __restrict__ n_rows, int slots) {
+  using S = SplitMma<2>;
+  constexpr int NPL = 2, W_SLICE = w_slice(NPL), WSL = NPL * 3 * 2 * 64, NCHUNK = CIN / 16, NCB = COUT / 64, NJ = COUT / 32;
+  __shared__ u32x4 Wp[NCB * WSL];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6, lx = lane & 31, half = lane >> 5;
+  const int b = blockIdx.y, n = min(n_rows[b], slots), m0 = blockIdx.x * 128;
+  if (m0 >= n) return;
+  const int row = m0 + wv * 32 + lx;
+  const int cell = row < n ? cell_rows[(size_t)b * slots + row] : -1;
+  const int cy = cell / W, cx = cell - cy * W;
+  const unsigned short* pl = in + (size_t)b * planes_image_pixels(H, W) * CIN * 2;
+
+  f32x16 acc[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
+
+  for (int c = 0; c < NCHUNK; ++c)
+    for (int dy = 0; dy < 3; ++dy) {
+      __syncthreads();  // every wave is done with the previous slice
+#pragma unroll
+      for (int cb = 0; cb < NCB; ++cb) {
+        const u32x4* src = (const u32x4*)(wx + ((size_t)(cb * NCHUNK + c) * 3 + dy) * W_SLICE);
+#pragma unroll
+        for (int i = 0; i < WSL / 256; ++i) lds_dma16(src + wv * 64 + 256 * i + lane, &Wp[cb * WSL + wv * 64 + 256 * i]);
+      }
+      // this lane's A operands of the kernel row: element (pixel, chunk c, plane p, k-half) of the PIN layout, or zero padding
+      u32x4 fa[3][NPL];
+      const int gy = cy + dy - 1;
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx) {
+        const int gx = cx + dx - 1;
+        const bool ok = cell >= 0 && gy >= 0 && gy < H && gx >= 0 && gx < W;
+        const int pix = ok ? gy * W + gx : 0;
+        const unsigned short* p0 = pl + (size_t)(pix >> 1) * (4 * CIN) + c * 64 + (pix & 1) * 32 + half * 8;
+#pragma unroll
+        for (int p = 0; p < NPL; ++p) {
+          fa[dx][p] = u32x4{0u, 0u, 0u, 0u};
+          if (ok) fa[dx][p] = *(const u32x4*)(p0 + p * 16);
+        }
+      }
+      lds_dma_wait_all();
+      __syncthreads();
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          u32x4 fb[NPL];
+#pragma unroll
+          for (int p = 0; p < NPL; ++p) fb[p] = Wp[(j >> 1) * WSL + ((p * 3 + dx) * 2 + half) * 64 + (j & 1) * 32 + lx];
+#pragma unroll
+          for (int tm = 0; tm < S::NT; ++tm) acc[j] = S::mma(fa[dx][S::ta(tm)], fb[S::tb(tm)], acc[j]);
+        }
+      __builtin_amdgcn_s_setprio(0);
+    }
+
+  // rows past n_rows[b] lie beyond the descriptor: dropped by the hardware
+  const dim_rsrc rs = buf_rsrc(out + (size_t)b * slots * COUT, (size_t)n * COUT * 4);
+  float vmax = 0.0f;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int co = j * 32 + lx;
+    const float bv = bias[co], inv_scale = inv_ch[co];
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+      const int r0 = m0 + wv * 32 + mfma_row(r, half);   // r even: the odd register is the next row
+      float v0 = acc[j][r] * inv_scale + bv, v1 = acc[j][r + 1] * inv_scale + bv;
+      if (relu) { v0 = fmaxf(v0, 0.0f); v1 = fmaxf(v1, 0.0f); }
+      vmax = sat_track(vmax, r0 < n ? v0 : 0.0f, r0 + 1 < n ? v1 : 0.0f);
+      const unsigned o0 = ((unsigned)r0 * (unsigned)COUT + (unsigned)co) * 4u;
+      buf_store_f32(rs, o0, v0);
+      buf_store_f32(rs, o0 + (unsigned)COUT * 4u, v1);
+    }
+  }
+  sat_report(sat, vmax);
+}
+
 // debug / inspection: pre-split planes back to fp32 (h + l is exact in fp32; / 16 undoes the activation scale)
 __global__ __launch_bounds__(256) void planes_to_f32_kernel(const unsigned short* __restrict__ planes, int C, int hw, float* __restrict__ out, size_t n) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;   // i = (image * hw + pixel) * C + channel
@@ -551,6 +642,18 @@ int launch_conv3x3_x6_planes(const float* in, const SplitWeights& wt, const floa
   else DIM_CONV6P_IO(128, 0)
 #undef DIM_CONV6P_IO
 #undef DIM_CONV6P
+  DIM_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_conv3x3_x6_rows(const float* in_planes, const SplitWeights& wt, const float* bias, float* out_rows, int batch, int H, int W, int cin, int cout,
+                           int relu, const int* cell_rows, const int* n_rows, int slots, hipStream_t s, unsigned* sat) {
+  DIM_REQUIRE(cin == 128 && cout == 256, "conv3x3_x6 rows: cin=%d cout=%d (the 128 -> 256 shape only)", cin, cout);
+  DIM_REQUIRE(wt.dev && wt.mode == 2, "conv3x3_x6 rows: fp16x3 weights required (mode %d)", wt.mode);
+  DIM_REQUIRE(cell_rows && n_rows && slots > 0 && (size_t)slots * cout * 4 < 0x7FFFFFF0ull, "conv3x3_x6 rows: bad row list (%d slots)", slots);
+  if (batch <= 0 || H <= 0 || W <= 0) return 0;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_x6_rows_kernel<128, 256>), dim3(cdiv(slots, 128), batch), dim3(256), 0, s, (const unsigned short*)in_planes,
+                     wt.dev, bias, out_rows, H, W, relu, wt.inv_ch(), sat, cell_rows, n_rows, slots);
   DIM_LAUNCH_CHECK();
   return 0;
 }

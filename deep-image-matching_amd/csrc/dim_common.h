@@ -332,7 +332,7 @@ void dim_sat_host_bump(int site);  // a range violation established on the host 
 // return the handle's override while the scope is open on this thread, else the process default; and (b) the device memory the handle
 // owns: everything a dim_*_create (or a lazily built debug buffer) allocates goes through dim_dev_alloc / dim_upload* below and is freed
 // by the one dim_handle_release its dim_*_destroy calls.  (Bodies: api_ops.hip.)
-constexpr int DIM_TUNE_KEYS = 19;
+constexpr int DIM_TUNE_KEYS = 21;
 constexpr unsigned DIM_HANDLE_MAGIC = 0x44494d48u;   // "DIMH"
 struct DimTune {
   int v[DIM_TUNE_KEYS];

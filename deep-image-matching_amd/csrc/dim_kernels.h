@@ -105,6 +105,11 @@ int launch_conv3x3_x6_fused1a(const float* image, const float* w1a_tap_cout, con
 // fp16x3 only: input and / or output pre-split in the bytes of the fp32 NHWC tensor: per pixel and 16-channel group, 16 h then 16 l fp16 pieces (conv_x6.hip)
 int launch_conv3x3_x6_planes(const float* in, const SplitWeights& wt, const float* bias, float* out, int batch, int H, int W, int cin,
                              int cout, int pool, int relu, int planes_in, int planes_out, hipStream_t s, unsigned* sat = nullptr, int bn = 0);
+// fp16x3, pre-split input, 128 -> 256 channels: the convolution at the listed pixels only.  Row r of image b is pixel cell_rows[b * slots + r],
+// r < n_rows[b] (device counts, <= slots); out_rows [batch][slots][cout] fp32, bit-identical per row to launch_conv3x3_x6_planes at that pixel.
+int launch_conv3x3_x6_rows(const float* in_planes, const SplitWeights& wt, const float* bias, float* out_rows, int batch, int H, int W, int cin, int cout,
+                           int relu, const int* cell_rows, const int* n_rows, int slots, hipStream_t s, unsigned* sat = nullptr);
+int dim_sparse_desc();     // dim_tune_set key 20.  1 (default): SuperPoint's descriptor head runs on the cells that keypoints sample when the rule of sp_api.hip picks it; 0: never; 2: whenever it can
 // Winograd F(2,3)-along-x variant of the fused conv1a + 3x3 convolution (conv_wg.hip): fp16x3 only, 2/3 of the MFMAs
 size_t conv_wino_weight_elems(int cin, int cout);
 void prepare_conv_weights_wino(const float* w_oihw, int cin, int cout, unsigned short* out, SplitWeights* sw);

@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "../../include/dim_hip.h"
@@ -35,9 +36,49 @@ struct dim_sp {
   float* b1_dbg;      // fp32 copy of conv1b's pooled output (dim_sp_debug_conv1b)
   float* x_dbg;       // fp32 copy of it, built on request by dim_sp_debug_buffers
   bool bn;            // dim_spo_create: the encoder layers' bias buffers are [b | s | t] and their convolutions run the BatchNorm epilogue
+  // sparse descriptor head (allocated on its first use, like the dense da / dd on theirs): the cells that keypoints sample, compact rows of convDa / convDb
+  float *da_rows, *dd_rows;
+  int *cell_rows, *n_rows, *row_of_cell;
+  int desc_slots;     // rows per image of the last sparse extract; 0: the last extract ran the dense head
 };
 
 namespace {
+// The sparse descriptor head is chosen when its worst-case row count min(4 capacity, h w) is at most this fraction of the map's cells: the measured
+// crossover at 1024^2 (profiles/sp_sparse_desc_ab.json).  Known on the host: no synchronisation.
+constexpr double kSparseDescMaxFraction = 0.8;
+
+int sp_alloc_dense_desc(dim_sp* h) {
+  const size_t cells = (size_t)h->max_batch * (h->max_h / 8) * (h->max_w / 8);
+  if (!h->da) DIM_TRY(dim_dev_alloc(&h->base, &h->da, cells * 256));
+  if (!h->dd) DIM_TRY(dim_dev_alloc(&h->base, &h->dd, cells * 256));
+  return 0;
+}
+int sp_alloc_sparse_desc(dim_sp* h) {
+  const size_t hw = (size_t)(h->max_h / 8) * (h->max_w / 8), B = h->max_batch;
+  const size_t slots = std::min((size_t)4 * h->capacity, hw);
+  if (!h->da_rows) DIM_TRY(dim_dev_alloc(&h->base, &h->da_rows, B * slots * 256));
+  if (!h->dd_rows) DIM_TRY(dim_dev_alloc(&h->base, &h->dd_rows, B * slots * 256));
+  if (!h->cell_rows) DIM_TRY(dim_dev_alloc(&h->base, &h->cell_rows, B * slots));
+  if (!h->row_of_cell) DIM_TRY(dim_dev_alloc(&h->base, &h->row_of_cell, B * hw));
+  if (!h->n_rows) DIM_TRY(dim_dev_alloc(&h->base, &h->n_rows, B));
+  return 0;
+}
+// the dense descriptor head on the last batch's encoder output (dim_sp_extract's dense path; dim_sp_debug_buffers after a sparse extract)
+int sp_dense_desc(dim_sp* h, int batch, int hh, int ww, int pmode, bool planes, unsigned* sat_head, bool prof, hipStream_t s) {
+  DIM_TRY(sp_alloc_dense_desc(h));
+  if (prof) dim_prof_begin(DIM_PROF_SP_CONVDA, s);
+  if (planes) DIM_RUN(launch_conv3x3_x6_planes(h->x, h->wsp[2][10], h->bias[10], h->da, batch, hh, ww, 128, 256, 0, 1, 1, 0, s, sat_head, 0));
+  else if (pmode != 0) DIM_RUN(launch_conv3x3_x6(h->x, h->wsp[pmode][10], h->bias[10], h->da, batch, hh, ww, 128, 256, 0, 1, s, sat_head, 0));
+  else DIM_RUN(launch_conv3x3(h->x, h->wk[10], h->bias[10], h->da, batch, hh, ww, 128, 256, 0, 1, s));
+  if (prof) dim_prof_end(DIM_PROF_SP_CONVDA, s);
+  GemmArgs g;
+  g.A0 = h->da; g.lda0 = 256; g.B = h->wk[11]; g.ldb = 256; g.bias = h->bias[11];
+  g.C = h->dd; g.ldc = 256; g.M = batch * hh * ww; g.N = 256; g.K = 256;
+  if (pmode != 0) { g.set_split(h->wsp[pmode][11]); DIM_RUN(launch_gemm_x6(g, 1, s)); }
+  else DIM_RUN(launch_gemm(g, 1, s));
+  return 0;
+}
+
 const int kCin[12] = {1, 64, 64, 64, 64, 128, 128, 128, 128, 256, 128, 256};
 const int kCout[12] = {64, 64, 64, 64, 128, 128, 128, 128, 256, 65, 256, 256};
 const int kK[12] = {3, 3, 3, 3, 3, 3, 3, 3, 3, 1, 3, 1};
@@ -59,6 +100,8 @@ int sp_create(const dim_sp_weights* w, const std::vector<float>* bn_st, const di
   h->max_batch = max_batch; h->max_h = max_h; h->max_w = max_w; h->capacity = capacity;
   h->last_h = h->last_w = h->last_batch = 0;
   h->b1_dbg = nullptr; h->x_dbg = nullptr; h->head_fused = false;
+  h->da = h->dd = nullptr;   // the dense descriptor maps (3.4 GB at 100 x 1024^2): allocated on the first dense use
+  h->da_rows = h->dd_rows = nullptr; h->cell_rows = h->n_rows = h->row_of_cell = nullptr; h->desc_slots = 0;
   h->bn = bn_st != nullptr;
   // ---- weights: OIHW (SPN:128-143) -> [tap][cin][cout] / [cin][cout_padded4] ----
   for (int l = 0; l < 12; ++l) {
@@ -118,8 +161,6 @@ int sp_create(const dim_sp_weights* w, const std::vector<float>* bn_st, const di
   DIM_TRY(dim_dev_alloc(hb, &h->x, B * dim_planes_image_pixels(hh, ww) * 128));
   DIM_TRY(dim_dev_alloc(hb, &h->pa, B * hh * ww * 256));
   DIM_TRY(dim_dev_alloc(hb, &h->logits, B * hh * ww * 65));
-  DIM_TRY(dim_dev_alloc(hb, &h->da, B * hh * ww * 256));
-  DIM_TRY(dim_dev_alloc(hb, &h->dd, B * hh * ww * 256));
   DIM_TRY(dim_dev_alloc(hb, &h->smap, B * hh * ww * 64));
   DIM_TRY(dim_dev_alloc(hb, &h->nms, B * hh * ww * 64));
   DIM_TRY(dim_dev_alloc(hb, &h->cand_score, B * hh * ww * 64));
@@ -285,17 +326,27 @@ int dim_sp_extract(dim_sp* h, const float* images_dev, int batch, int H, int W, 
                        h->ncand, h->cand_score, h->cand_idx, s));
   DIM_RUN(launch_topk(h->cand_score, h->cand_idx, h->ncand, batch, H8, W8, h->cfg.max_keypoints, h->capacity, kpts_xy_dev,
                      scores_dev, n_kpts_dev, h->topk_keys, 0, s));
-  // descriptor head (SPN:213-221)
-  if (planes) SP_SITE(DIM_PROF_SP_CONVDA, convp(10, h->x, h->da, hh, ww, 128, 256, 0, 1, 0));
-  else SP_SITE(DIM_PROF_SP_CONVDA, conv(10, h->x, h->da, hh, ww, 128, 256, 0));
-  {
+  // descriptor head (SPN:213-221).  The keypoints are known: with few enough of them convDa / convDb run only on the cells that the sampler will
+  // read (at most four per keypoint), listed on the device in raster order; per cell the arithmetic is the dense path's, bit for bit.  The sparse
+  // form exists for the pre-split fp16x3 encoder output; keep-all handles (max_keypoints = -1) and everything else stay dense.
+  const int slots = (int)std::min((size_t)4 * h->capacity, (size_t)hh * ww);
+  const int sparse_sel = dim_sparse_desc();
+  const bool sparse = planes && (sparse_sel == 2 || (sparse_sel == 1 && h->cfg.max_keypoints > 0 && (double)slots <= kSparseDescMaxFraction * (double)hh * ww));
+  if (sparse) {
+    DIM_RUN(sp_alloc_sparse_desc(h));
+    DIM_RUN(launch_desc_cell_list(kpts_xy_dev, n_kpts_dev, batch, hh, ww, h->capacity, h->cfg.fix_sampling, slots, h->row_of_cell, h->cell_rows, h->n_rows, s));
+    SP_SITE(DIM_PROF_SP_CONVDA, launch_conv3x3_x6_rows(h->x, h->wsp[2][10], h->bias[10], h->da_rows, batch, hh, ww, 128, 256, 1, h->cell_rows, h->n_rows, slots, s, sat_head));
     GemmArgs g;
-    g.A0 = h->da; g.lda0 = 256; g.B = h->wk[11]; g.ldb = 256; g.bias = h->bias[11];
-    g.C = h->dd; g.ldc = 256; g.M = batch * hh * ww; g.N = 256; g.K = 256;
-    if (x6) { g.set_split(h->wsp[pmode][11]); DIM_RUN(launch_gemm_x6(g, 1, s)); }
-    else DIM_RUN(launch_gemm(g, 1, s));
+    g.A0 = h->da_rows; g.lda0 = 256; g.strideA0 = (long long)slots * 256; g.B = h->wk[11]; g.ldb = 256; g.bias = h->bias[11];
+    g.C = h->dd_rows; g.ldc = 256; g.strideC = (long long)slots * 256; g.M = slots; g.N = 256; g.K = 256; g.rows = h->n_rows;
+    g.set_split(h->wsp[2][11]);
+    DIM_RUN(launch_gemm_x6(g, batch, s));
+    DIM_RUN(launch_sample_desc(h->dd_rows, kpts_xy_dev, n_kpts_dev, desc_dev, batch, hh, ww, h->capacity, h->cfg.fix_sampling, s, h->row_of_cell, slots));
+  } else {
+    DIM_RUN(sp_dense_desc(h, batch, hh, ww, pmode, planes, sat_head, true, s));
+    DIM_RUN(launch_sample_desc(h->dd, kpts_xy_dev, n_kpts_dev, desc_dev, batch, hh, ww, h->capacity, h->cfg.fix_sampling, s));
   }
-  DIM_RUN(launch_sample_desc(h->dd, kpts_xy_dev, n_kpts_dev, desc_dev, batch, hh, ww, h->capacity, h->cfg.fix_sampling, s));
+  h->desc_slots = sparse ? slots : 0;
 #undef SP_SITE
   h->last_h = hh; h->last_w = ww; h->last_batch = batch;
   return 0;
@@ -327,7 +378,13 @@ int dim_sp_debug_buffers(dim_sp* h, const float** encoder, const float** logits,
   }
   if (score_map) *score_map = h->smap;
   if (nms_map) *nms_map = h->nms;
-  if (dense_desc) *dense_desc = h->dd;
+  if (dense_desc) {
+    if (h->desc_slots > 0 && h->last_batch > 0) {   // the sparse head stored only the sampled cells: rebuild the dense map from the last batch's encoder output
+      if (sp_dense_desc(h, h->last_batch, h->last_h, h->last_w, 2, true, nullptr, false, nullptr) != 0) return -1;
+      DIM_HIP(hipDeviceSynchronize());
+    } else if (sp_alloc_dense_desc(h) != 0) return -1;
+    *dense_desc = h->dd;
+  }
   if (h8) *h8 = h->last_h * 8;
   if (w8) *w8 = h->last_w * 8;
   return 0;
@@ -349,6 +406,13 @@ int dim_sp_debug_conv1b(dim_sp* h, int batch, int H, int W, const float** out_f3
   *out_f32 = h->b1_dbg;
   if (h2) *h2 = H2;
   if (w2) *w2 = W2;
+  return 0;
+}
+
+int dim_sp_desc_rows(dim_sp* h, const int32_t** n_rows_dev, int* slots) {
+  DIM_REQUIRE(h && slots, "dim_sp_desc_rows: null argument");
+  *slots = h->desc_slots;
+  if (n_rows_dev) *n_rows_dev = h->desc_slots > 0 ? h->n_rows : nullptr;
   return 0;
 }
 

@@ -19,5 +19,11 @@ int launch_topk(const float* cand_score, const int* cand_idx, const int* ncand, 
 // (DKD's top-k mode, ALN:150-151)
 int launch_topk_zero_fill(const float* nms, int batch, int H8, int W8, float thr, int border, int k, int capacity, float* kpts, float* scores,
                           int* n_out, hipStream_t s);
+// row_of_cell != nullptr: `dense` holds `slots` compact descriptor rows per image and row_of_cell [batch][h w] maps a cell to its row
 int launch_sample_desc(const float* dense, const float* kpts, const int* n_kpts, float* desc, int batch, int h, int w,
-                       int capacity, int fix_sampling, hipStream_t s);
+                       int capacity, int fix_sampling, hipStream_t s, const int* row_of_cell = nullptr, int slots = 0);
+// The cells of the [h][w] descriptor map that launch_sample_desc will read for these keypoints (up to four corners each, corners outside the
+// map left out), per image in raster order: cell_rows [batch][slots], their count n_rows [batch] and the inverse row_of_cell [batch][h w]
+// (-1 = not needed).  slots >= min(4 capacity, h w).  Three launches, no host read.
+int launch_desc_cell_list(const float* kpts, const int* n_kpts, int batch, int h, int w, int capacity, int fix_sampling, int slots, int* row_of_cell,
+                          int* cell_rows, int* n_rows, hipStream_t s);

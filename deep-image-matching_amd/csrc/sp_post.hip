@@ -608,15 +608,9 @@ __global__ __launch_bounds__(1024) void topk_zero_fill_kernel(const float* __res
 }
 
 // ---------------------------------------------------------------------------
-// one wave per keypoint; lane owns channels 4*lane .. 4*lane+3 of the 256.
-__global__ __launch_bounds__(256) void sample_desc_kernel(const float* __restrict__ dense, const float* __restrict__ kpts,
-                                                          const int* __restrict__ n_kpts, float* __restrict__ desc, int h,
-                                                          int w, int capacity, int fix_sampling) {
-  const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
-  if (i >= n_kpts[b]) return;
-  const float kx = kpts[((size_t)b * capacity + i) * 2], ky = kpts[((size_t)b * capacity + i) * 2 + 1];
-  float ix, iy;
+// Where a keypoint samples the [h][w] descriptor map: both samplers' coordinate arithmetic, shared by sample_desc_kernel and by the marker of
+// the cells it will read (mark_desc_cells_kernel), so the two cannot disagree.  Corners: (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1).
+__device__ __forceinline__ void sp_desc_corner(float kx, float ky, int h, int w, int fix_sampling, float& ix, float& iy, int& x0, int& y0) {
   if (fix_sampling) {  // SPX:16-27: (k + 0.5) / (w*8), align_corners=False
     float gx = (kx + 0.5f) / ((float)w * 8.0f), gy = (ky + 0.5f) / ((float)h * 8.0f);
     gx = gx * 2.0f - 1.0f; gy = gy * 2.0f - 1.0f;
@@ -628,12 +622,27 @@ __global__ __launch_bounds__(256) void sample_desc_kernel(const float* __restric
     ix = ((gx + 1.0f) / 2.0f) * (float)(w - 1);
     iy = ((gy + 1.0f) / 2.0f) * (float)(h - 1);
   }
+  x0 = (int)floorf(ix); y0 = (int)floorf(iy);
+}
+
+// one wave per keypoint; lane owns channels 4*lane .. 4*lane+3 of the 256.  row_of_cell == nullptr: `dense` is the [batch][h][w][256] map;
+// otherwise `dense` holds `slots` compact rows per image and row_of_cell[b][cell] is the row of a cell (launch_desc_cell_list marked every cell
+// read here, so the entry is never -1).
+__global__ __launch_bounds__(256) void sample_desc_kernel(const float* __restrict__ dense, const float* __restrict__ kpts,
+                                                          const int* __restrict__ n_kpts, float* __restrict__ desc, int h,
+                                                          int w, int capacity, int fix_sampling, const int* __restrict__ row_of_cell, int slots) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
+  if (i >= n_kpts[b]) return;
+  const float kx = kpts[((size_t)b * capacity + i) * 2], ky = kpts[((size_t)b * capacity + i) * 2 + 1];
+  float ix, iy;
+  int x0, y0;
+  sp_desc_corner(kx, ky, h, w, fix_sampling, ix, iy, x0, y0);
   const float fx = floorf(ix), fy = floorf(iy);
-  const int x0 = (int)fx, y0 = (int)fy;
   // bilinear weights exactly as ATen's grid_sampler: nw, ne, sw, se
   const float wnw = (fx + 1.0f - ix) * (fy + 1.0f - iy), wne = (ix - fx) * (fy + 1.0f - iy);
   const float wsw = (fx + 1.0f - ix) * (iy - fy), wse = (ix - fx) * (iy - fy);
-  const float* base = dense + (size_t)b * h * w * 256;
+  const float* base = dense + (size_t)b * (row_of_cell ? (size_t)slots : (size_t)h * w) * 256;
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   const int cxs[4] = {x0, x0 + 1, x0, x0 + 1};
   const int cys[4] = {y0, y0, y0 + 1, y0 + 1};
@@ -642,7 +651,11 @@ __global__ __launch_bounds__(256) void sample_desc_kernel(const float* __restric
   for (int c = 0; c < 4; ++c) {
     const bool in = cxs[c] >= 0 && cxs[c] < w && cys[c] >= 0 && cys[c] < h;  // wave-uniform
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (in) v = *(const float4*)(base + ((size_t)cys[c] * w + cxs[c]) * 256 + lane * 4);
+    if (in) {
+      size_t row = (size_t)cys[c] * w + cxs[c];
+      if (row_of_cell) row = (size_t)row_of_cell[(size_t)b * h * w + row];
+      v = *(const float4*)(base + row * 256 + lane * 4);
+    }
     float ss = wave_sum(v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w);
     const float den = fmaxf(sqrtf(ss), 1e-12f);  // F.normalize of the dense map (SPN:215)
     if (in) {
@@ -654,6 +667,54 @@ __global__ __launch_bounds__(256) void sample_desc_kernel(const float* __restric
   const float den = fmaxf(sqrtf(ss), 1e-12f);  // SPN:95-97
   *(float4*)(desc + ((size_t)b * capacity + i) * 256 + lane * 4) =
       make_float4(acc[0] / den, acc[1] / den, acc[2] / den, acc[3] / den);
+}
+
+// ---------------------------------------------------------------------------
+// The cells of the descriptor map that sample_desc_kernel will read (launch_desc_cell_list): mark, then compact in raster order.
+// row_of_cell doubles as the mark: -1 (the launcher's fill) = not needed, 0 = marked.  Every writer stores the same value, so the result does not
+// depend on the order in which the stores arrive.
+__global__ __launch_bounds__(256) void mark_desc_cells_kernel(const float* __restrict__ kpts, const int* __restrict__ n_kpts, int h, int w, int capacity,
+                                                              int fix_sampling, int* __restrict__ row_of_cell) {
+  const int i = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+  if (i >= min(n_kpts[b], capacity)) return;
+  const float kx = kpts[((size_t)b * capacity + i) * 2], ky = kpts[((size_t)b * capacity + i) * 2 + 1];
+  float ix, iy;
+  int x0, y0;
+  sp_desc_corner(kx, ky, h, w, fix_sampling, ix, iy, x0, y0);
+  int* m = row_of_cell + (size_t)b * h * w;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int cx = x0 + (c & 1), cy = y0 + (c >> 1);
+    if (cx >= 0 && cx < w && cy >= 0 && cy < h) m[cy * w + cx] = 0;
+  }
+}
+
+// one workgroup per image: count / scan / emit over the marks.  Thread t owns the `per` consecutive cells from t * per, so the emitted order is
+// the raster order.  At most `slots` = min(4 capacity, h w) cells can be marked (four per keypoint).
+__global__ __launch_bounds__(1024) void compact_desc_cells_kernel(int* __restrict__ row_of_cell, int* __restrict__ cell_rows, int* __restrict__ n_rows,
+                                                                  int hw, int slots) {
+  __shared__ int part[1024];
+  const int t = threadIdx.x, b = blockIdx.x;
+  int* m = row_of_cell + (size_t)b * hw;
+  const int per = (hw + 1023) / 1024;
+  const int c0 = min(t * per, hw), c1 = min(c0 + per, hw);
+  int sum = 0;
+  for (int c = c0; c < c1; ++c) sum += m[c] >= 0 ? 1 : 0;
+  part[t] = sum;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {
+    int v = (t >= off) ? part[t - off] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  int run = part[t] - sum;
+  for (int c = c0; c < c1; ++c)
+    if (m[c] >= 0) {
+      if (run < slots) { cell_rows[(size_t)b * slots + run] = c; m[c] = run; }
+      ++run;
+    }
+  if (t == 1023) n_rows[b] = min(part[1023], slots);
 }
 
 }  // namespace
@@ -741,9 +802,19 @@ int launch_topk_zero_fill(const float* nms, int batch, int H8, int W8, float thr
 }
 
 int launch_sample_desc(const float* dense, const float* kpts, const int* n_kpts, float* desc, int batch, int h, int w,
-                       int capacity, int fix_sampling, hipStream_t s) {
+                       int capacity, int fix_sampling, hipStream_t s, const int* row_of_cell, int slots) {
   if (batch <= 0 || capacity <= 0) return 0;
-  hipLaunchKernelGGL(sample_desc_kernel, dim3(cdiv(capacity, 4), batch), dim3(256), 0, s, dense, kpts, n_kpts, desc, h, w, capacity, fix_sampling);
+  hipLaunchKernelGGL(sample_desc_kernel, dim3(cdiv(capacity, 4), batch), dim3(256), 0, s, dense, kpts, n_kpts, desc, h, w, capacity, fix_sampling, row_of_cell, slots);
+  DIM_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_desc_cell_list(const float* kpts, const int* n_kpts, int batch, int h, int w, int capacity, int fix_sampling, int slots, int* row_of_cell,
+                          int* cell_rows, int* n_rows, hipStream_t s) {
+  if (batch <= 0 || capacity <= 0 || h <= 0 || w <= 0) return 0;
+  DIM_HIP(hipMemsetAsync(row_of_cell, 0xFF, (size_t)batch * h * w * sizeof(int), s));   // -1 everywhere
+  hipLaunchKernelGGL(mark_desc_cells_kernel, dim3(cdiv(capacity, 256), batch), dim3(256), 0, s, kpts, n_kpts, h, w, capacity, fix_sampling, row_of_cell);
+  hipLaunchKernelGGL(compact_desc_cells_kernel, dim3(batch), dim3(1024), 0, s, row_of_cell, cell_rows, n_rows, h * w, slots);
   DIM_LAUNCH_CHECK();
   return 0;
 }

@@ -69,6 +69,22 @@ class SuperPointHIP(capi.ResidentHandle):
             return out.cpu()
         return torch.frombuffer((ctypes.c_int32 * batch).from_address(p.value), dtype=torch.int32).clone()
 
+    def desc_rows(self, batch: int):
+        """How the last call ran the descriptor head (dim_sp_desc_rows; synchronises): None when it ran on the whole map, otherwise
+        (slots, n_rows) — the rows reserved per image and a host int32 tensor [batch] with the number of distinct cells the keypoints sample."""
+        p, slots = ctypes.c_void_p(), ctypes.c_int()
+        capi.check(self.lib, self.lib.dim_sp_desc_rows(self._h, ctypes.byref(p), ctypes.byref(slots)))
+        if slots.value == 0:
+            return None
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+            out = torch.empty(batch, dtype=torch.int32, device=self.device)
+            rc = ctypes.CDLL("libamdhip64.so").hipMemcpy(ctypes.c_void_p(out.data_ptr()), p, ctypes.c_size_t(batch * 4), 3)
+            if rc != 0:
+                raise capi.DimHipError(f"hipMemcpy failed: {rc}")
+            return slots.value, out.cpu()
+        return slots.value, torch.frombuffer((ctypes.c_int32 * batch).from_address(p.value), dtype=torch.int32).clone()
+
     @torch.no_grad()
     def extract_batch(self, images: torch.Tensor, out=None):
         """images [B,H,W] float32 in [0,1] on self.device.  Returns device tensors

@@ -62,6 +62,9 @@ int dim_device_synchronize(void);
  *          set) 16-row tiles with LDS-DMA weight staging); key 6  split-precision GEMM block (1 default: 128 x 256 when the launch fills the
  *          GPU, 0 = always 128 x 128, 2 = always 128 x 256); key 7  simple_nms tiles (1 default: 64 x 64 on large maps, 0 = 32 x 32,
  *          2 = always 64 x 64); key 10  ALIKED fp16x3 convolution tile rows (16 default, 8, 17 = 16 with streamed weights).
+ *   key 20 SuperPoint's descriptor head: 1 (default) convDa / convDb run only on the cells that the keypoints sample when at most 0.8 of the map's
+ *          cells can be needed (min(4 capacity, h w) <= 0.8 h w, max_keypoints > 0, fp16x3 with pre-split activations), 0 = always on the whole
+ *          map, 2 = on the sampled cells whenever the arithmetic allows (the tests; bit-identical descriptors either way).  (19 is not a key.)
  * Keys 12-15 do not exist in this library: they select research prototypes and timing probes that are compiled only into
  * libdim_hip_research.so (build.build_variant("research", ["-DDIM_RESEARCH"]); csrc/dim_kernels.h) and return an error here.
  * dim_handle_tune_set(handle, key, value) overrides a key for ONE extractor / matcher handle (value < 0: back to the process default). */
@@ -164,6 +167,10 @@ int dim_sp_debug_buffers(dim_sp* h, const float** encoder, const float** logits,
 /* fp32 NHWC copy [batch][H/2][W/2][64] of conv1b's pooled output (SPN:162-163) of the last dim_sp_extract call on (batch, H, W):
  * A/B of the convolution variants (dim_tune_set keys 2, 3, 5).  Synchronises the device. */
 int dim_sp_debug_conv1b(dim_sp* h, int batch, int H, int W, const float** out_f32, int* h2, int* w2);
+
+/* How the last dim_sp_extract ran the descriptor head.  *slots = 0: on the whole map (*n_rows_dev = NULL).  Otherwise on listed cells: *slots rows
+ * were reserved per image and n_rows_dev [batch] (device int32 owned by the handle) holds the number of distinct cells the keypoints sample. */
+int dim_sp_desc_rows(dim_sp* h, const int32_t** n_rows_dev, int* slots);
 
 /* Number of NMS survivors above threshold/border per image of the last call
  * (before top-k), device int32 [batch] owned by the handle. */
