@@ -29,8 +29,9 @@ struct AttnArgs6 {
   long long sq, sk, sv, so;
   const int* n; const int* done;
   int cross;
+  int rotary;            // 1: the rotary embedding is applied to q and k (LightGlue's self attention); 0: cross attention, and SuperGlue (no rotary at all)
   float scale;
-  const float* enc;      // [items][nmax][64] cos|sin; rotary is applied to q (and k) iff !cross
+  const float* enc;      // [items][nmax][64] cos|sin; read iff rotary
   u32x4* kv_img;         // [items][4 heads][tiles][1536] pre-split K|V tile images (kv_prep_kernel)
   int nmax, tiles;
   int splits;            // key range cut into `splits` parts per (query block, head, item): small batches only
@@ -67,7 +68,7 @@ __global__ __launch_bounds__(256) void kv_prep_kernel(AttnArgs6 a) {
       const float* p = kb + (size_t)(kt + key) * a.ldk + d0;
       const float4 x0 = *(const float4*)p, x1 = *(const float4*)(p + 8);
       x[0] = x0.x; x[1] = x0.y; x[2] = x0.z; x[3] = x0.w; x[4] = x1.x; x[5] = x1.y; x[6] = x1.z; x[7] = x1.w;
-      if (!a.cross) {
+      if (a.rotary) {
         const float* e = a.enc + ((size_t)item * a.nmax + kt + key) * 64 + (d0 >> 1);  // pairs d0/2, d0/2 + 1, d0/2 + 4, d0/2 + 5
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -159,7 +160,7 @@ __global__ __launch_bounds__(256, (MODE == 2 ? 4 : 2)) void attn_x6_kernel(AttnA
       if (qok) {
         const float4 x0 = *(const float4*)(qp + 16 * s), x1 = *(const float4*)(qp + 16 * s + 8);
         x[0] = x0.x; x[1] = x0.y; x[2] = x0.z; x[3] = x0.w; x[4] = x1.x; x[5] = x1.y; x[6] = x1.z; x[7] = x1.w;
-        if (!a.cross) {  // rotary (LGN:41-54,155): pair i of the lane <-> frequency 8s + 2half + (i & 1) + 4 (i >> 1)
+        if (a.rotary) {  // rotary (LGN:41-54,155): pair i of the lane <-> frequency 8s + 2half + (i & 1) + 4 (i >> 1)
           const float* e = a.enc + ((size_t)item * a.nmax + qrow) * 64 + 8 * s + 2 * half;
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
@@ -383,14 +384,15 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(AttnArgs6 a, float ou
 int launch_lg_attention_x6(const LgState& st, int cross, hipStream_t s, int kv_ready) {
   AttnArgs6 a;
   const long long is = (long long)st.nmax * 768;
-  if (!cross) { a.q = st.qkv; a.k = st.qkv + 256; a.v = st.qkv + 512; }
+  // st.sg (SuperGlue, sg_api.hip): three separate projections [q | k | v] in self AND cross layers (k, v then come from the other item), no rotary
+  if (!cross || st.sg) { a.q = st.qkv; a.k = st.qkv + 256; a.v = st.qkv + 512; }
   else { a.q = st.qkv; a.k = st.qkv; a.v = st.qkv + 256; }
   a.ldq = a.ldk = a.ldv = 768; a.sq = a.sk = a.sv = is;
   a.o = st.ctx; a.ldo = 256; a.so = (long long)st.nmax * 256;
-  a.n = st.n_cur; a.done = st.done; a.cross = cross;
+  a.n = st.n_cur; a.done = st.done; a.cross = cross; a.rotary = (!cross && !st.sg) ? 1 : 0;
   a.scale = 0.125f;
   a.sat = st.sat_qkv;
-  a.q_img = (kv_ready && cross) ? 1 : 0;
+  a.q_img = (kv_ready && cross && !st.sg) ? 1 : 0;
   a.enc = st.enc; a.kv_img = (u32x4*)st.kv_img; a.nmax = st.nmax; a.tiles = cdiv(st.nmax, 32);
   // small batches leave most CUs idle and make every workgroup walk all key tiles alone: cut the key range
   const int nsel = st.nsel > 0 ? st.nsel : st.nmax;   // rows that can be live in this call: the query blocks / merge rows beyond them would only exit
@@ -399,8 +401,8 @@ int launch_lg_attention_x6(const LgState& st, int cross, hipStream_t s, int kv_r
   // ... into the fewest parts (1, 2, 4) that give the launch two workgroups per CU (512).  (Until round 6: 4 parts up to 128 workgroups, 2 up to 256, else 1 —
   // one pair of 2304 keypoints ran 288 workgroups of 36 tiles, 1.1 per CU: 2.01 ms against 1.52 at 2048; three pairs of 2048 ran 384 of 64 tiles.)
   a.splits = (st.attn_part && st.n_items <= st.attn_part_items) ? (wgs >= 512 ? 1 : (wgs >= 256 ? 2 : 4)) : 1;
-  a.probe = cross ? dim_attn_probe() : 0;
-  if (a.probe == 2) a.splits = 16;  // probe 2: every query block's key range in 16 parts -> the partial-record volume of a shared score tile, written AND merged
+  a.probe = (cross && !st.sg) ? dim_attn_probe() : 0;   // (the timing probes are LightGlue's: a SuperGlue handle has no partial-record scratch)
+  if (a.probe == 2 && st.attn_part != nullptr) a.splits = 16;  // probe 2: every query block's key range in 16 parts -> the partial-record volume of a shared score tile, written AND merged
   if (dim_attn_probe() == 8 || dim_attn_probe() == 16) { a.probe = 0; if (a.splits > 1) a.splits = dim_attn_probe(); }   // research: a finer key split for small batches (results stay correct)
   const bool two_ahead = dim_attn_probe() == 22;   // research, 22: the key-split launches with TWO tiles of prefetch distance (prototype; results identical, measured slower)
   if (two_ahead) a.probe = 0;

@@ -39,6 +39,9 @@ struct LgState {  // device pointers owned by the handle
   // lg_attn_d96.hip: desc / ctx / msg / md rows of 96, enc rows of 96 = cos[48] | sin[48], qkv rows of 288, hid rows of 192, kv_img
   // [items][tiles][2304 x 16 B], attn_part [items][nmax][4][100])
   int dim = 256, heads = 4, head_dim = 64;
+  // SuperGlue (sg_api.hip) on the 256-wide kernels: qkv rows are three SEPARATE projections [q | k | v] in self and cross layers alike and there is no
+  // rotary embedding; launch_lg_attention_x6 then never takes Q from the K image
+  int sg = 0;
 };
 
 int launch_lg_init(const LgState& st, const float* kpts_tab, const float* desc_tab, const int* n_tab, const float* size_tab,

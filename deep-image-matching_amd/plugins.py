@@ -12,7 +12,8 @@ matcher_base.py:36-60); otherwise a minimal stand-in base with the same construc
 ``KorniaMatcher`` mirrors matchers/kornia_matcher.py:9-53 (nearest-neighbour descriptor matching, no weights);
 ``SuperPointOpenExtractor`` mirrors extractors/superpoint_open.py:72-164 (the openly licensed SuperPoint);
 ``XfeatExtractor`` mirrors extractors/xfeat.py:11-63 (XFeat's sparse detectAndCompute);
-``LighterGlueMatcher`` mirrors matchers/lighterglue.py:78-241 (the matcher of the shipped ``xfeat+lighterglue`` pipeline).
+``LighterGlueMatcher`` mirrors matchers/lighterglue.py:78-241 (the matcher of the shipped ``xfeat+lighterglue`` pipeline);
+``SuperGlueMatcher`` mirrors matchers/superglue.py:54-106 (the matcher of the shipped ``superpoint+superglue`` pipeline).
 See INTEGRATION.md for the module files a maintainer adds to the reference tree.
 """
 from __future__ import annotations
@@ -32,6 +33,7 @@ from .aliked_hip import AlikedHIP
 from .lightglue_hip import LightGlueHIP
 from .lighterglue_hip import LighterGlueHIP
 from .nn_hip import NearestNeighborHIP, check_mode as _check_nn_mode
+from .superglue_hip import SuperGlueHIP
 from .superpoint_hip import SuperPointHIP, SuperPointOpenHIP
 from .tile_matching import BatchedTileMatchingMixin
 from .tiling import BatchedTilingMixin
@@ -838,6 +840,83 @@ class LighterGlueMatcher(_LightGluePairMixin, _MatcherBase):
         f0 = {**feats0, "image_size": self._size_as_the_network_sees_it(feats0)}
         f1 = {**feats1, "image_size": self._size_as_the_network_sees_it(feats1)}
         return super()._match_pairs(f0, f1).astype(np.int32)
+
+
+class SuperGlueMatcher(_ResidentMatcherMixin, _MatcherBase):
+    """matchers/superglue.py:54 — SuperGlue on the gfx950 library, quirks included: the class's ``default_config`` (20 iterations / 0.3) is never
+    merged (MatcherBase merges ``_default_conf``, empty in the base), so a matcher section without ``sinkhorn_iterations`` / ``match_threshold``
+    runs the NETWORK's defaults, 100 / 0.2 (SGN:212-219); ``weights`` must be "indoor" or "outdoor" (SGN:244); ``scores`` and ``image_size`` are
+    required; ``image_size`` (H, W) gives image0 its shape (1, 1, H, W), so the network normalises with width = image_size[1]; every other key of
+    the feature dicts is ignored; the result is the (S, 2) int64 array of (i, matches0[i]), ascending in i.  Both per-call values are read from
+    the config at every call.  No BatchedTileMatchingMixin: tiled pairs go through the reference's per-pair tile loop as they are."""
+
+    default_config = {"name": "superglue", "weights": "outdoor", "sinkhorn_iterations": 20, "match_threshold": 0.3}   # (as in the reference: not merged)
+    _default_conf: dict = {}
+    required_inputs = []
+    min_matches = 20
+    max_feat_no_tiling = 50000
+    _network_conf = {"weights": "outdoor", "sinkhorn_iterations": 100, "match_threshold": 0.2}   # SuperGlue.default_config (SGN:212-219)
+
+    def __init__(self, config) -> None:
+        super().__init__(config)
+        self._lib = capi.load()
+        self._device = _resolve_device(self._device, "SuperGlueMatcher")
+        cfg = {**self._network_conf, **self.config.get("matcher", {})}
+        if cfg["weights"] not in ("indoor", "outdoor"):
+            raise ValueError(f"SuperGlue weights must be 'indoor' or 'outdoor', got {cfg['weights']!r}")
+        self._arith = _apply_arithmetic(cfg, self._lib)
+        self._on_sat = _saturation_policy(cfg)
+        path = cfg.get("weights_path")
+        if path is None and not os.environ.get("DIM_SUPERGLUE_WEIGHTS") and cfg.get("allow_synthetic_weights"):
+            logger.warning("SuperGlue: running on seeded SYNTHETIC weights (allow_synthetic_weights) - test / benchmark use only")
+        self._sd = _weights.load_superglue_state_dict(path, allow_synthetic=bool(cfg.get("allow_synthetic_weights", False)))
+        self._net: Optional[SuperGlueHIP] = None
+        self._net_n = 0
+
+    def _new_net(self, pairs: int, n: int) -> SuperGlueHIP:
+        return SuperGlueHIP(self._sd, None, max_pairs=pairs, max_kpts=n, device=self._dev(), lib=self._lib, on_saturation=self._on_sat, arithmetic=self._arith)
+
+    def _ensure(self, n: int):
+        # the score block is max_kpts^2 floats: the handle follows the pair in steps of 1024 (a 4096-row floor as LightGlue's would pin 64 MiB for
+        # nothing, the shipped configuration's 8000 keypoints take 256 MiB)
+        if self._net is None or n > self._net_n:
+            on_gpu = str(getattr(self._dev(), "type", self._dev())).startswith("cuda")
+            self._net_n = max(1024 if on_gpu else 64, (max(n, 1) + 1023) // 1024 * 1024 if on_gpu else 1 << (max(n, 1) - 1).bit_length())
+            self._net = self._new_net(1, self._net_n)
+
+    @torch.no_grad()
+    def _match_pairs(self, feats0: dict, feats1: dict) -> np.ndarray:
+        """feats: numpy dicts as read from features.h5 (keypoints (N, 2), descriptors (256, N) — or (N, 256) —, scores (N,), float16 or float32,
+        image_size (H, W), + ignored keys).  Returns (S, 2) int64 index pairs."""
+        cfg = {**self._network_conf, **self.config.get("matcher", {})}
+        iters, thr = int(cfg["sinkhorn_iterations"]), float(cfg["match_threshold"])
+        fs = []
+        for f in (feats0, feats1):
+            for key in ("scores", "image_size"):
+                if key not in f:
+                    raise ValueError(f"{key} not found in features - required by SuperGlue")
+            g = featuresDict2Lightglue({k: f[k] for k in ("keypoints", "descriptors", "scores", "image_size")})
+            size = np.asarray(g["image_size"], dtype=np.float32).astype(int).reshape(-1)   # matchers/superglue.py:38: float, then int
+            fs.append((np.asarray(g["keypoints"], dtype=np.float32), np.asarray(g["descriptors"], dtype=np.float32),
+                       np.asarray(g["scores"], dtype=np.float32).reshape(-1), (int(size[0]), int(size[1]))))
+        (k0, d0, s0, hw0), (k1, d1, s1, hw1) = fs
+        m, n = k0.shape[0], k1.shape[0]
+        if m == 0 or n == 0:   # SGN:255-262: nothing matches
+            return np.zeros((0, 2), dtype=np.int64)
+        if d0.shape[1] != 256 or d1.shape[1] != 256:
+            raise ValueError(f"descriptor dimension {d0.shape} / {d1.shape}: SuperGlue takes 256-wide descriptors")
+        self._ensure(max(m, n))
+        net = self._net
+        dev = torch.device(net.device)
+        cap = max(m, n)
+        kt, dt, sc = np.zeros((2, cap, 2), np.float32), np.zeros((2, cap, 256), np.float32), np.zeros((2, cap), np.float32)
+        kt[0, :m], kt[1, :n], dt[0, :m], dt[1, :n], sc[0, :m], sc[1, :n] = k0, k1, d0, d1, s0, s1
+        st = np.array([[hw0[1], hw0[0]], [hw1[1], hw1[0]]], dtype=np.float32)   # the library takes (width, height)
+        up = lambda a: torch.from_numpy(a).to(dev)   # noqa: E731
+        o = net.match_batch_guarded(up(kt), up(dt), up(sc), torch.tensor([m, n], dtype=torch.int32, device=dev), up(st), n_pairs=1,
+                                    sinkhorn_iterations=iters, match_threshold=thr, logger=logger)
+        S = int(o["n_matches"][0].item())
+        return o["matches"][0, :S].cpu().numpy().astype(np.int64)
 
 
 class KorniaMatcher(_ResidentMatcherMixin, BatchedTileMatchingMixin, _MatcherBase):

@@ -522,3 +522,141 @@ def load_xfeat_state_dict(path: str | None = None, seed: int = 21, allow_synthet
     sd = {k: (v.float().contiguous() if v.is_floating_point() else v) for k, v in sd.items()}
     validate_xfeat_state_dict(sd)
     return sd
+
+
+# ---- SuperGlue (thirdparty/SuperGluePretrainedNetwork/models/superglue.py, SGN) ----------------------------------------------------------
+SUPERGLUE_KENC = [3, 32, 64, 128, 256, 256]   # SGN:79,215: MLP([3] + keypoint_encoder + [descriptor_dim])
+SUPERGLUE_BN_EPS = 1e-5
+_SG_BN = ("weight", "bias", "running_mean", "running_var")
+
+
+def superglue_n_layers(sd: Dict[str, torch.Tensor]) -> int:
+    """len(GNN_layers) as the state dict has it (gnn.layers.{i}.*)."""
+    idx = {int(k.split(".")[2]) for k in sd if k.startswith("gnn.layers.")}
+    return max(idx) + 1 if idx else 0
+
+
+def superglue_state_dict_shapes(n_layers: int = 18) -> Dict[str, tuple]:
+    """Every tensor SuperGlueHIP reads, by the module's key (Conv1d weights keep their kernel axis)."""
+    sh = {"bin_score": (), "final_proj.weight": (256, 256, 1), "final_proj.bias": (256,)}
+    c = SUPERGLUE_KENC
+    for s in range(5):
+        sh[f"kenc.encoder.{3 * s}.weight"] = (c[s + 1], c[s], 1)
+        sh[f"kenc.encoder.{3 * s}.bias"] = (c[s + 1],)
+        if s < 4:
+            sh.update({f"kenc.encoder.{3 * s + 1}.{n}": (c[s + 1],) for n in _SG_BN})
+    for i in range(n_layers):
+        t = f"gnn.layers.{i}."
+        for nm in ("attn.merge", "attn.proj.0", "attn.proj.1", "attn.proj.2"):
+            sh[t + nm + ".weight"], sh[t + nm + ".bias"] = (256, 256, 1), (256,)
+        sh[t + "mlp.0.weight"], sh[t + "mlp.0.bias"] = (512, 512, 1), (512,)
+        sh.update({t + f"mlp.1.{n}": (512,) for n in _SG_BN})
+        sh[t + "mlp.3.weight"], sh[t + "mlp.3.bias"] = (256, 512, 1), (256,)
+    return sh
+
+
+def validate_superglue_state_dict(sd: Dict[str, torch.Tensor]) -> int:
+    """Checks keys and shapes; returns the layer count (a positive multiple of 2: self / cross alternate, SGN:216)."""
+    n_layers = superglue_n_layers(sd)
+    if n_layers == 0 or n_layers % 2:
+        raise ValueError(f"SuperGlue checkpoint: {n_layers} GNN layers (gnn.layers.*), expected a positive multiple of 2")
+    for k, shape in superglue_state_dict_shapes(n_layers).items():
+        if k not in sd:
+            raise KeyError(f"SuperGlue checkpoint lacks '{k}'")
+        if tuple(sd[k].shape) != shape:
+            raise ValueError(f"SuperGlue checkpoint: '{k}' has shape {tuple(sd[k].shape)}, expected {shape}")
+    return n_layers
+
+
+def synthetic_superglue_state_dict(seed: int = 0, n_layers: int = 18, final_gain: float = 14.0, delta_gain: float = 0.25,
+                                   bin_score: float = 2.0) -> Dict[str, torch.Tensor]:
+    """Seeded synthetic weights with which the network really matches: variance-preserving convolutions, BatchNorm layers with non-trivial
+    running statistics, the last convolution of every residual mlp damped by ``delta_gain`` (18 layers stay inside the fp16 split's range and
+    keep corresponding descriptors close), final_proj = ``final_gain`` x a random orthogonal matrix (scores = gain^2 / 16 x the cosine)."""
+    g = torch.Generator().manual_seed(seed)
+    sd: Dict[str, torch.Tensor] = {}
+
+    def conv(name, co, ci, gain=1.0, bias=0.02):
+        sd[name + ".weight"] = torch.randn(co, ci, 1, generator=g) * (gain / math.sqrt(ci))
+        sd[name + ".bias"] = torch.randn(co, generator=g) * bias
+
+    def bn(name, c):
+        sd[name + ".weight"] = 0.6 + 0.8 * torch.rand(c, generator=g)
+        sd[name + ".bias"] = 0.1 * torch.randn(c, generator=g)
+        sd[name + ".running_mean"] = 0.1 * torch.randn(c, generator=g)
+        sd[name + ".running_var"] = 0.5 + torch.rand(c, generator=g)
+        sd[name + ".num_batches_tracked"] = torch.tensor(1000)
+
+    c = SUPERGLUE_KENC
+    for s in range(5):
+        conv(f"kenc.encoder.{3 * s}", c[s + 1], c[s], gain=1.4 if s < 4 else 0.05)
+        if s < 4:
+            bn(f"kenc.encoder.{3 * s + 1}", c[s + 1])
+    sd["kenc.encoder.12.bias"] = torch.zeros(256)   # SGN:80
+    for i in range(n_layers):
+        t = f"gnn.layers.{i}."
+        conv(t + "attn.merge", 256, 256)
+        for j in range(3):
+            conv(t + f"attn.proj.{j}", 256, 256, gain=4.0 if j < 2 else 1.0)
+        conv(t + "mlp.0", 512, 512, gain=1.4)
+        bn(t + "mlp.1", 512)
+        conv(t + "mlp.3", 256, 512, gain=delta_gain)
+        sd[t + "mlp.3.bias"] = torch.zeros(256)   # SGN:124
+    q, _ = torch.linalg.qr(torch.randn(256, 256, generator=g, dtype=torch.float64))
+    sd["final_proj.weight"] = (final_gain * q).float()[:, :, None].contiguous()
+    sd["final_proj.bias"] = torch.randn(256, generator=g) * 0.01
+    sd["bin_score"] = torch.tensor(float(bin_score))
+    return sd
+
+
+def superglue_head_permutation() -> torch.Tensor:
+    """perm[h * 64 + d] = d * 4 + h: the module's attention channel (view(b, 64, 4, n), SGN:112) behind every head-major device channel."""
+    c = torch.arange(256)
+    return (c % 64) * 4 + c // 64
+
+
+def prepare_superglue_weights(sd: Dict[str, torch.Tensor], dtype=torch.float32) -> Dict[str, torch.Tensor]:
+    """What dim_sg_create takes: (out, in) fp32 matrices with BatchNorm1d (eval) folded into the convolution in front of it and the attention
+    channels permuted to head-major (rows of proj.0-2, columns of merge).  All arithmetic in fp64, rounded once (``dtype`` = torch.float64: not
+    at all — what the host-side test compares with the unfolded module)."""
+    n_layers = validate_superglue_state_dict(sd)
+    d = lambda k: sd[k].detach().double()
+    mat = lambda k: d(k).reshape(sd[k].shape[0], sd[k].shape[1])
+
+    def folded(conv, norm):
+        s = d(norm + ".weight") / torch.sqrt(d(norm + ".running_var") + SUPERGLUE_BN_EPS)
+        return mat(conv + ".weight") * s[:, None], (d(conv + ".bias") - d(norm + ".running_mean")) * s + d(norm + ".bias")
+
+    out: Dict[str, torch.Tensor] = {}
+    for s in range(5):
+        if s < 4:
+            out[f"kenc.{s}.w"], out[f"kenc.{s}.b"] = folded(f"kenc.encoder.{3 * s}", f"kenc.encoder.{3 * s + 1}")
+        else:
+            out[f"kenc.{s}.w"], out[f"kenc.{s}.b"] = mat("kenc.encoder.12.weight"), d("kenc.encoder.12.bias")
+    perm = superglue_head_permutation()
+    for i in range(n_layers):
+        t = f"gnn.layers.{i}."
+        for j, nm in enumerate("qkv"):
+            out[f"{i}.{nm}_w"], out[f"{i}.{nm}_b"] = mat(t + f"attn.proj.{j}.weight")[perm], d(t + f"attn.proj.{j}.bias")[perm]
+        out[f"{i}.merge_w"], out[f"{i}.merge_b"] = mat(t + "attn.merge.weight")[:, perm], d(t + "attn.merge.bias")
+        out[f"{i}.mlp0_w"], out[f"{i}.mlp0_b"] = folded(t + "mlp.0", t + "mlp.1")
+        out[f"{i}.mlp3_w"], out[f"{i}.mlp3_b"] = mat(t + "mlp.3.weight"), d(t + "mlp.3.bias")
+    out["final_proj.w"], out["final_proj.b"] = mat("final_proj.weight"), d("final_proj.bias")
+    out = {k: v.to(dtype).contiguous() for k, v in out.items()}
+    out["bin_score"] = sd["bin_score"].detach().to(dtype).reshape(())
+    return out
+
+
+def load_superglue_state_dict(path: str | None = None, seed: int = 0, allow_synthetic: bool = False) -> Dict[str, torch.Tensor]:
+    """superglue_{indoor,outdoor}.pth (SGN:244-247), shapes validated.  ``path`` None: the DIM_SUPERGLUE_WEIGHTS environment variable, else
+    (opt-in) synthetic weights."""
+    import os
+
+    path = path or os.environ.get("DIM_SUPERGLUE_WEIGHTS") or None
+    if path is None:
+        _no_weights("SuperGlue (superglue_outdoor.pth / superglue_indoor.pth, SGN:244-247)", "DIM_SUPERGLUE_WEIGHTS", allow_synthetic)
+        return synthetic_superglue_state_dict(seed)
+    sd = torch.load(str(Path(path)), map_location="cpu")
+    sd = {k: (v.float().contiguous() if v.is_floating_point() else v) for k, v in sd.items()}
+    validate_superglue_state_dict(sd)
+    return sd

@@ -418,6 +418,61 @@ int dim_lg_match(dim_lg* h, const float* kpts_tab_dev, const float* desc_tab_dev
 int dim_lg_debug_desc(dim_lg* h, const float** desc, const int32_t** n_cur, const int32_t** ind);
 
 /* ------------------------------------------------------------------------ */
+/* Resident SuperGlue matcher (reference thirdparty/SuperGluePretrainedNetwork/
+ * models/superglue.py, SGN; csrc/sg_api.hip, sg_kernels.hip)                */
+/* ------------------------------------------------------------------------ */
+/* Weights as the HOST prepares them (weights.prepare_superglue_weights, fp64): BatchNorm1d (eval, eps 1e-5) folded into the convolution in
+ * front of it, and the attention channels permuted from the module's c = d * 4 + h (view(b, 64, 4, n), SGN:112) to head-major c = h * 64 + d:
+ * the ROWS of the three projections and the COLUMNS of merge.  Conv1d(kernel 1) weights are (out, in) row-major, fp32, finite. */
+typedef struct dim_sg_layer_weights {
+  const float *q_w, *q_b, *k_w, *k_b, *v_w, *v_b; /* attn.proj.{0,1,2}: (256,256),(256,) rows head-major */
+  const float *merge_w, *merge_b;                 /* attn.merge: (256,256) columns head-major */
+  const float *mlp0_w, *mlp0_b;                   /* mlp.0 with mlp.1 (BatchNorm) folded: (512,512) over [x | message] */
+  const float *mlp3_w, *mlp3_b;                   /* mlp.3: (256,512) */
+} dim_sg_layer_weights;
+typedef struct dim_sg_weights {
+  const float* kenc_w[5];  /* kenc.encoder.{0,3,6,9,12}, BatchNorm folded into the first four: (32,3),(64,32),(128,64),(256,128),(256,256) */
+  const float* kenc_b[5];
+  const float *final_proj_w, *final_proj_b; /* (256,256),(256,) */
+  float bin_score;
+  const dim_sg_layer_weights* layers;       /* [n_layers]: self, cross, self, ... (SGN:216) */
+} dim_sg_weights;
+typedef struct dim_sg_config {
+  int n_layers;        /* len(GNN_layers), read from the state dict: a positive multiple of 2 */
+  int descriptor_dim;  /* 256 */
+} dim_sg_config;
+typedef struct dim_sg dim_sg;
+
+/* Device memory of a handle, N = max_kpts rounded up to 4, P = max_pairs: the score block P * N * N floats (N = 8192, P = 1: 256 MiB;
+ * N = 2048, P = 16: 256 MiB), the graph network's activations 2 P N * 2304 floats and the K | V tile images 2 P N * 3072 bytes
+ * (N = 8192, P = 1: 144 + 48 MiB).  The (N+1) x (N+1) coupling matrix of the reference is never built. */
+int dim_sg_create(const dim_sg_weights* w, const dim_sg_config* cfg, int max_pairs, int max_kpts, dim_sg** out);
+void dim_sg_destroy(dim_sg* h);
+int dim_sg_max_kpts(dim_sg* h);
+/* Matches n_pairs pairs in one call.  The feature table is dim_lg_match's (kpts_tab_dev [n_img][cap][2], desc_tab_dev [n_img][cap][256],
+ * n_tab_dev, pair_idx_dev) plus score_tab_dev [n_img][cap], the detection scores the keypoint encoder reads.  size_tab_dev [n_img][2] holds
+ * (width, height).  sinkhorn_iterations (>= 0) and match_threshold are per call.  Outputs as dim_lg_match (NK = dim_sg_max_kpts(h)):
+ * matches_dev [n_pairs][NK][2] int64 (idx0 ascending), mscores_dev [n_pairs][NK], n_matches_dev [n_pairs], matches01_dev [n_pairs][2][NK]
+ * int32 (-1 = unmatched), mscores01_dev [n_pairs][2][NK].  A pair with an empty side gives -1 / 0 everywhere (SGN:255-262).  Runs in the
+ * split arithmetics (dim_tune_set key 1 = 2 or 1) under the fp16x3 range guard; only enqueues work on `stream`. */
+int dim_sg_match(dim_sg* h, const float* kpts_tab_dev, const float* desc_tab_dev, const float* score_tab_dev, const int32_t* n_tab_dev,
+                 const float* size_tab_dev, int cap, const int32_t* pair_idx_dev, int n_pairs, int sinkhorn_iterations, float match_threshold,
+                 int64_t* matches_dev, float* mscores_dev, int32_t* n_matches_dev, int32_t* matches01_dev, float* mscores01_dev, void* stream);
+/* DEBUG ONLY — dim_sg_debug, dim_sg_debug_layers, dim_sg_sinkhorn, dim_sg_select exist for the parity tests and the stage benchmark; they are not
+ * part of the stable ABI and may change or go without a DIM_HIP_ABI_VERSION bump.  A handle with dim_sg_debug_layers set is not a matcher.
+ * Parity taps and operator-level tests: the handle's buffers — descriptors [2 P][NK][256] (after the last layer), the score block
+ * [P][NK][NK], u and v [P][NK + 1] (pair of m x n: u[m], v[n] = the dustbin entries), the live counts [2 P] and the per-pair skip flags [P]
+ * (0 = run, non-zero = empty pair).  dim_sg_sinkhorn / dim_sg_select run the two stages behind the score product on whatever these buffers
+ * hold (rows per image <= cap, as in dim_sg_match): what dim_sg_match itself calls. */
+int dim_sg_debug(dim_sg* h, float** desc, float** scores, float** u, float** v, int32_t** n_cur, int32_t** done);
+/* Parity taps: later dim_sg_match calls stop the graph network after n_layers layers (0: the descriptors tap holds the keypoint encoder's
+ * output; < 0: all layers, the default). */
+int dim_sg_debug_layers(dim_sg* h, int n_layers);
+int dim_sg_sinkhorn(dim_sg* h, int n_pairs, int cap, int sinkhorn_iterations, void* stream);
+int dim_sg_select(dim_sg* h, int n_pairs, int cap, float match_threshold, int64_t* matches_dev, float* mscores_dev, int32_t* n_matches_dev,
+                  int32_t* matches01_dev, float* mscores01_dev, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Nearest-neighbour descriptor matching (reference matchers/kornia_matcher.py:
  * kornia.feature.DescriptorMatcher(match_mode, th); csrc/nn_match.hip)      */
 /* ------------------------------------------------------------------------ */
