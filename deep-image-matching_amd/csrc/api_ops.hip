@@ -4,6 +4,7 @@
 #include <stdio.h>
 
 #include "../../include/dim_hip.h"
+#include "lg_kernels.h"
 #include "sp_kernels.h"
 
 static thread_local char g_err[1024] = "";
@@ -363,6 +364,99 @@ int dim_op_ffn_fused_f32(const float* A, int lda, const void* w0_x3, const float
   g.C = C; g.ldc = ldc; g.M = M; g.N = 512; g.K = K;
   g.sat = dim_sat_counter(DIM_SAT_OP); g.sat2 = dim_sat_counter(DIM_SAT_OP);
   return launch_gemm_x6(g, 1, (hipStream_t)stream);
+}
+
+// LightGlue / LighterGlue / SuperGlue attention as the matchers run it (lg_api.hip, lgl_api.hip, sg_api.hip): an LgState over the caller's tensors, the K | V
+// tile images and the key-split partial records carved out of the caller's workspace (256-byte aligned pieces; nothing is allocated here), then the
+// matchers' own launchers.
+namespace {
+struct LgAttentionWs {
+  size_t kv_img, part, total;   // byte offsets
+};
+LgAttentionWs lg_attention_ws(int width, int n_items, int nmax, int split_items) {
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t tiles = (size_t)cdiv(nmax, 32);
+  LgAttentionWs w;
+  w.kv_img = 0;
+  // [items][4 heads][tiles][KV_TILE_STRIDE x 16 B] (lg_attn_x6.hip) / [items][tiles][2304 x 16 B] (lg_attn_d96.hip)
+  w.part = up(width == 256 ? (size_t)n_items * 4 * tiles * KV_TILE_STRIDE * 16 : (size_t)n_items * tiles * 2304 * 16);
+  // [split_items][4 heads][nmax][4 parts][68] / [split_items][nmax][4 parts][100] floats
+  w.total = w.part + up(split_items > 0 ? (size_t)split_items * nmax * 4 * (width == 256 ? 4 * 68 : 100) * sizeof(float) : 0);
+  return w;
+}
+int lg_attention_state(LgState& st, const char* who, int width, int kind, float* qkv, const float* enc, const int32_t* n_dev, const int32_t* done_dev,
+                       float* ctx, int n_items, int nmax, int nsel, int split_items, void* workspace) {
+  DIM_REQUIRE(width == 256 || width == 96, "%s: width %d (256: four heads of 64; 96: one head)", who, width);
+  DIM_REQUIRE(kind >= 0 && kind <= (width == 256 ? 3 : 1), "%s: kind %d at width %d (0 self, 1 cross; 2 / 3 SuperGlue self / cross at width 256)", who, kind, width);
+  DIM_REQUIRE(qkv && n_dev && done_dev && ctx && workspace, "%s: null argument", who);
+  DIM_REQUIRE(enc || kind != 0, "%s: self attention (kind 0) needs the rotary table", who);
+  DIM_REQUIRE(n_items >= 2 && n_items % 2 == 0, "%s: n_items %d must be a positive even number (item = 2 * pair + side)", who, n_items);
+  DIM_REQUIRE(nmax > 0 && nsel > 0 && nsel <= nmax && split_items >= 0, "%s: need 0 < nsel %d <= nmax %d and split_items %d >= 0", who, nsel, nmax, split_items);
+  DIM_REQUIRE((long long)n_items * nmax * 3 * width <= 0x7fffffffLL, "%s: %d items of %d rows exceed 2^31 elements", who, n_items, nmax);
+  const LgAttentionWs w = lg_attention_ws(width, n_items, nmax, split_items);
+  char* base = (char*)workspace;
+  st.n_pairs = n_items / 2; st.n_items = n_items; st.nmax = nmax; st.nsel = nsel;
+  st.qkv = qkv; st.ctx = ctx; st.enc = (float*)enc; st.n_cur = (int*)n_dev; st.done = (int*)done_dev;
+  st.kv_img = base + w.kv_img;
+  st.attn_part = split_items > 0 ? (float*)(base + w.part) : nullptr;
+  st.attn_part_items = split_items;
+  st.sat_qkv = dim_sat_counter(DIM_SAT_OP);
+  st.sg = kind >= 2 ? 1 : 0;
+  if (width == 96) { st.dim = 96; st.heads = 1; st.head_dim = 96; }
+  return 0;
+}
+}  // namespace
+
+size_t dim_op_lg_attention_workspace_bytes(int width, int n_items, int nmax, int split_items) {
+  if ((width != 256 && width != 96) || n_items <= 0 || nmax <= 0 || split_items < 0) return 0;
+  return lg_attention_ws(width, n_items, nmax, split_items).total;
+}
+
+int dim_op_lg_attention_f32(int width, int kind, float* qkv, const float* enc, const int32_t* n_dev, const int32_t* done_dev, float* ctx, int n_items,
+                            int nmax, int nsel, int split_items, void* workspace, void* stream) {
+  LgState st{};
+  int rc = lg_attention_state(st, "dim_op_lg_attention_f32", width, kind, qkv, enc, n_dev, done_dev, ctx, n_items, nmax, nsel, split_items, workspace);
+  if (rc != 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int mode = dim_precision_mode();
+  if (width == 96) return launch_lgl_attention(st, kind, s);   // (refuses the fp32 arithmetic itself)
+  if (kind >= 2) {   // as dim_sg_match
+    DIM_REQUIRE(mode == 1 || mode == 2, "dim_op_lg_attention_f32: SuperGlue attention exists in the split arithmetics (fp16x3, bf16x6) only, not fp32");
+    return launch_lg_attention_x6(st, kind & 1, s, 0);
+  }
+  if (mode == 0 && kind == 0) {   // the split kernels rotate q and k while they load them; the fp32 kernel reads them rotated (dim_lg_match)
+    rc = launch_lg_rotary(st, s);
+    if (rc != 0) return rc;
+  }
+  return launch_lg_attention(st, kind, s, 0);
+}
+
+int dim_op_lg_qkv_attention_f32(int kind, const float* x, const void* w_x3, const float* bias, const float* enc, const int32_t* n_dev,
+                                const int32_t* done_dev, float* qkv, float* ctx, int n_items, int nmax, int nsel, int split_items, void* workspace,
+                                void* stream) {
+  const char* who = "dim_op_lg_qkv_attention_f32";
+  DIM_REQUIRE(kind == 0 || kind == 1, "%s: kind %d (0 self, 1 cross)", who, kind);
+  DIM_REQUIRE(x && w_x3 && bias, "%s: null argument", who);
+  const SplitWeights& W = *(const SplitWeights*)w_x3;
+  const int N = kind == 0 ? 768 : 512;
+  DIM_REQUIRE(dim_precision_mode() == 2 && W.mode == 2 && W.n_pad == N, "%s: needs the fp16x3 arithmetic and an fp16x3 weight handle of 256 x %d (dim_x3_create)", who, N);
+  LgState st{};
+  int rc = lg_attention_state(st, who, 256, kind, qkv, enc, n_dev, done_dev, ctx, n_items, nmax, nsel, split_items, workspace);
+  if (rc != 0) return rc;
+  DIM_REQUIRE(gemm_x6_fuses_kv(nsel, N, n_items, 2), "%s: the projection GEMM does not write K | V tile images at %d items of %d rows x %d columns "
+              "(gemm_x6_fuses_kv is false: neither the 128 x 256 nor the 32 x 128 block runs this shape)", who, n_items, nsel, N);
+  hipStream_t s = (hipStream_t)stream;
+  GemmArgs g;   // lg_api.hip gemm_qkv
+  g.A0 = x; g.lda0 = 256; g.strideA0 = (long long)nmax * 256;
+  g.bias = bias; g.C = qkv; g.ldc = 768; g.strideC = (long long)nmax * 768;
+  g.M = nsel; g.N = N; g.K = 256; g.rows = st.n_cur; g.flag = st.done; g.flag_shift = 1; g.flag_eq = 0;
+  g.sat = st.sat_qkv;
+  g.kv_img = st.kv_img; g.kv_tiles = cdiv(nmax, 32); g.kv_kblock = kind == 0 ? 1 : 0; g.kv_vblock = g.kv_kblock + 1; g.kv_nmax = nmax;
+  g.kv_enc = kind == 0 ? enc : nullptr;
+  g.set_split(W);
+  rc = launch_gemm_x6(g, n_items, s);
+  if (rc != 0) return rc;
+  return launch_lg_attention(st, kind, s, 1);
 }
 
 int dim_convx6_create(const float* w_oihw_host, int cin, int cout, void** out_dev) {

@@ -38,7 +38,11 @@ struct AttnArgs6 {
   int qblocks, groups;   // workgroups per (item, head) group = qblocks (incl. splits); groups = 4 * items (XCD-aware 1-D grid)
   float* part;           // [items][4][nmax][splits][PART] partial (unnormalised O, running max, running sum)
   int probe;             // timing probes of the shared-score-tile question (dim_tune_set key 12); 0 in the product
-  unsigned* sat;         // fp16x3 range guard on the rotated K (the rotation can grow |k| by sqrt 2) and on V
+  unsigned* sat;         // fp16x3 range guard on the rotated K only (the rotation can grow |k| by sqrt 2; kv_prep_kernel).  Intended asymmetry: V and the unrotated
+                         // q | k are stored — and reported — by the projection GEMM in front of every launch (its sat counter, the same site), so kv_prep does not
+                         // test V a second time; Q is multiplied by scale * log2(e) < 0.19 before its split, which more than undoes the rotation's sqrt 2.
+                         // (kv_prep96_kernel does test V: there K is also rescaled, and one maximum serves both.)  dim_op_lg_attention_f32 has no GEMM in
+                         // front: its contract (include/dim_hip.h) leaves |v| <= 4094 to the caller.
   int q_img;             // cross attention with images written by the projection GEMM (gemm_x6.hip KV): there is no fp32 qk —
                          // the Q operand is this item's own K image, and the softmax scale is applied to the scores instead
 };

@@ -547,6 +547,34 @@ int dim_op_ffn_fused_f32(const float* A, int lda, const void* w0_x3_handle, cons
                          const void* w3_x3_kperm_handle, const float* bias3, const float* residual, int ldr, float* C, int ldc, int M, int K,
                          void* stream);
 
+/* The matchers' attention on caller-supplied projections, through the launchers dim_lg_match / dim_sg_match run (csrc/lg_attn.hip, lg_attn_x6.hip,
+ * lg_attn_d96.hip; several launches: [rotary |] K | V pre-split, attention [, merge of a split key range]), in the arithmetic of dim_tune_set key 1.
+ *   width 256: 4 heads of 64, qkv rows of 768, enc rows cos[32] | sin[32], softmax scale 1/8.  fp16x3, bf16x6 or fp32.
+ *   width 96:  1 head of 96, qkv rows of 288, enc rows cos[48] | sin[48], scale 96^-0.5 (cross: 96^-0.25 on either side).  fp16x3 or bf16x6 only.
+ *   kind 0  LightGlue self: rows [q | k | v]; every pair (x[2f], x[2f + 1]) of a head of q and k is rotated by (cos[f], sin[f]) of its row (LGN:41-54).
+ *           In the fp32 arithmetic the rotation is written back: q and k of qkv come back rotated.
+ *   kind 1  LightGlue cross: rows [qk | v | unused]; item i attends to the keys and values of item i ^ 1, no rotation (enc may be NULL).
+ *   kind 2 / 3  SuperGlue self / cross (width 256, split arithmetics only): rows [q | k | v] in both, no rotation; 3 reads k, v of item i ^ 1.
+ * qkv [n_items][nmax][3 width], enc [n_items][nmax][64 | 96], ctx [n_items][nmax][width]: 16-byte aligned.  n_dev [n_items]: live
+ * rows per item, each <= nsel <= nmax (launch shapes follow nsel, strides follow nmax); done_dev [n_items / 2]: a pair with done != 0 is skipped.
+ * ctx row r of item i = softmax(q_r K^T scale) V over the first n[key item] keys; an empty key set gives a row of zeros.  Rows at or past n[i] and
+ * the rows of skipped pairs are not written, and no row of qkv at or past n[item] is read.
+ * split_items: 0 = the key range is never cut.  Otherwise, when n_items <= split_items, the launchers' own rule cuts it into 4, 2 or 1 parts for
+ * cdiv(nsel, 128) * heads * n_items below 256, below 512, or above (what the matchers do for small batches), and a merge kernel follows.
+ * workspace: dim_op_lg_attention_workspace_bytes(...) bytes, 16-byte aligned; nothing is read from it that this call has not written.
+ * fp16x3 range guard: DIM_SAT_OP counts |k| > 4094 after the rotation (width 96: after the rotation and the 96^-0.25 scale, and |v| as well).  At
+ * width 256 v is NOT checked here: in the matchers the projection GEMM that produces it reports it; a caller of this entry keeps |v| <= 4094. */
+size_t dim_op_lg_attention_workspace_bytes(int width, int n_items, int nmax, int split_items);
+int dim_op_lg_attention_f32(int width, int kind, float* qkv, const float* enc, const int32_t* n_dev, const int32_t* done_dev, float* ctx, int n_items,
+                            int nmax, int nsel, int split_items, void* workspace, void* stream);
+/* The large-batch form of dim_lg_match's attention (width 256, fp16x3, kind 0 | 1): the projection qkv = x W + bias (x [n_items][nmax][256], W from
+ * dim_x3_create(256, 768) for kind 0, (256, 512) for kind 1) writes the K | V tile images in its epilogue (rotary included), no pre-split pass runs, and
+ * cross attention takes its Q operand from the item's own K image.  qkv receives the fp32 projection (live rows), ctx as above.  An error when the
+ * projection GEMM does not fuse the images at this shape (n_items, nsel).  Same workspace; DIM_SAT_OP counts |q|, |k|, |v| > 4094 as well. */
+int dim_op_lg_qkv_attention_f32(int kind, const float* x, const void* w_x3_handle, const float* bias, const float* enc, const int32_t* n_dev,
+                                const int32_t* done_dev, float* qkv, float* ctx, int n_items, int nmax, int nsel, int split_items, void* workspace,
+                                void* stream);
+
 /* 3x3/s1/p1 conv, NHWC fp32, weights [9][cin][cout], bias+ReLU and optional
  * 2x2 max-pool fused (SPN:161-171).  cin in {64,128}, cout % 64 == 0. */
 int dim_op_conv3x3_nhwc_f32(const float* in, const float* w_tap_cin_cout, const float* bias, float* out, int batch,

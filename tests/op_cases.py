@@ -770,3 +770,404 @@ def check_sample(r):
 
 SAMPLE_CASES = [(5, 7, 3, 64, (0, 1, 64)), (12, 20, 2, 300, (300, 37))]       # (h, w, batch, capacity, n_kpts)
 SAMPLE_OCCUPANCY_CASE = (128, 128, 2, 2048, (2048, 2047))                       # cdiv(2048, 4) * 2 = 1024 workgroups (hardware only)
+
+
+# ---------------------------------------------------------------------------------------------------------------- attention (LightGlue, LighterGlue, SuperGlue)
+# dim_op_lg_attention_f32 / dim_op_lg_qkv_attention_f32 (include/dim_hip.h) = the matchers' launchers on caller-supplied projections:
+#   width 256  launch_lg_attention -> attn_kernel (fp32, behind launch_lg_rotary for kind 0) | launch_lg_attention_x6 -> kv_prep_kernel<MODE>,
+#              attn_x6_kernel<MODE> [, attn_combine_kernel<2 | 4>]
+#   width 96   launch_lgl_attention -> kv_prep96_kernel<MODE>, attn_d96_kernel<MODE> [, attn_combine96_kernel]
+# against a plain fp64 evaluation.  Figure: max |out - ref| / max|v|, max|v| per (key item, head), over the live rows.  Yardstick: the same figure of a
+# plain fp32 torch evaluation of the same fp32 inputs (fp32 rotary, matmul, softmax, matmul), the largest of ATTN_PERMS evaluations with permuted key
+# order.  Bound: ATTN_FACTOR x yardstick, the factor of the project's other fp32-accuracy claims (goldens, lighterglue attention_undamped, Sinkhorn).
+# An item is (n, seed): its rows depend on nothing else, so the same item can sit in calls of different sizes.
+ATTN_FACTOR, ATTN_PERMS = 2.0, 4
+LOG2E = 1.4426950408889634
+
+
+def _bind_attention(lib):
+    lib.dim_op_lg_attention_workspace_bytes.argtypes = [_ci, _ci, _ci, _ci]
+    lib.dim_op_lg_attention_workspace_bytes.restype = ctypes.c_size_t
+    lib.dim_op_lg_attention_f32.argtypes = [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp]
+    lib.dim_op_lg_attention_f32.restype = _ci
+    lib.dim_op_lg_qkv_attention_f32.argtypes = [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp]
+    lib.dim_op_lg_qkv_attention_f32.restype = _ci
+
+
+def attn_heads(width):
+    return (4, 64) if width == 256 else (1, 96)
+
+
+@functools.lru_cache(maxsize=None)
+def _attn_item(width, n, family, seed):
+    """One item: q, k [n][width] ~ gain randn, v ~ randn, enc [n][width / heads] = cos | sin of angles uniform in [0, 2 pi).  flat: gain 1 (logits within
+    about +-5).  ramp: gain 1.5 and k times linspace(0.2, 2, n) along the keys: the running maximum rises tile after tile."""
+    g = torch.Generator().manual_seed(seed)
+    gain = 1.5 if family == "ramp" else 1.0
+    q, k, v = gain * torch.randn(n, width, generator=g), gain * torch.randn(n, width, generator=g), torch.randn(n, width, generator=g)
+    if family == "ramp":
+        k = k * torch.linspace(0.2, 2.0, n)[:, None]
+    ang = torch.rand(n, attn_heads(width)[1] // 2, generator=g) * (2 * torch.pi)
+    return q, k, v, torch.cat([torch.cos(ang), torch.sin(ang)], dim=1)
+
+
+def _attn_rotate(x, enc):
+    """x [heads][n][hd], enc [n][hd] = cos[hd / 2] | sin[hd / 2]: the pairs (x[2f], x[2f + 1]) rotated by (cos[f], sin[f]), in x's precision."""
+    hf = enc.shape[1] // 2
+    c, s = enc[None, :, :hf].to(x.dtype), enc[None, :, hf:].to(x.dtype)
+    x0, x1 = x[..., 0::2], x[..., 1::2]
+    return torch.stack([x0 * c - x1 * s, x1 * c + x0 * s], dim=-1).flatten(-2)
+
+
+def _attn_split_rows(width, kind, rows):
+    """One item's qkv rows -> (q, k, v), each [n][width]."""
+    if kind == 1:
+        return rows[:, :width], rows[:, :width], rows[:, width:2 * width]
+    return rows[:, :width], rows[:, width:2 * width], rows[:, 2 * width:]
+
+
+def _attn_eval(width, kind, qkv, enc, n, dtype, perm_seed=None):
+    """softmax(q k^T scale) v per item and head in `dtype` over the first n[key item] keys (kind 1 / 3: the keys and values of item ^ 1), rotary on q and
+    k for kind 0; an empty key set gives zeros.  qkv [items][nmax][3 width] -> ([items][nmax][width] (rows past n: 0), per-item tile events).
+    perm_seed: the keys of every item are visited in a seeded random order.  events[i] = (a key tile of 32 whose maximum exceeds the running one by
+    more than 8 in log2, one that exceeds it by 0 .. 8), by the rule of the kernels: the running maximum only moves in the first case."""
+    heads, hd = attn_heads(width)
+    scale = 0.125 if width == 256 else 96.0 ** -0.5
+    I, nmax = qkv.shape[:2]
+    out = torch.zeros(I, nmax, width, dtype=dtype)
+    events = []
+    for i in range(I):
+        j = i ^ 1 if kind in (1, 3) else i
+        nq, nk = int(n[i]), int(n[j])
+        events.append((False, False))
+        if nq == 0 or nk == 0:
+            continue
+        q = _attn_split_rows(width, kind, qkv[i, :nq])[0].to(dtype).view(nq, heads, hd).transpose(0, 1)
+        _, k, v = _attn_split_rows(width, kind, qkv[j, :nk])
+        k, v = k.to(dtype).view(nk, heads, hd).transpose(0, 1), v.to(dtype).view(nk, heads, hd).transpose(0, 1)
+        if kind == 0:
+            q, k = _attn_rotate(q, enc[i, :nq]), _attn_rotate(k, enc[j, :nk])
+        if perm_seed is not None:
+            perm = torch.randperm(nk, generator=torch.Generator().manual_seed(perm_seed * 1000 + i))
+            k, v = k[:, perm], v[:, perm]
+        s = (q @ k.transpose(1, 2)) * scale
+        out[i, :nq] = (torch.softmax(s, dim=-1) @ v).transpose(0, 1).reshape(nq, width)
+        if perm_seed is None and nk > 32:
+            tiles = -(-nk // 32)
+            tm = F.pad(s * LOG2E, (0, tiles * 32 - nk), value=float("-inf")).view(heads, nq, tiles, 32).amax(dim=-1)
+            m, jump, defer = tm[..., 0], False, False
+            for t in range(1, tiles):
+                d = tm[..., t] - m
+                jump, defer = jump or bool((d > 8).any()), defer or bool(((d > 0) & (d <= 8)).any())
+                m = torch.where(d > 8, tm[..., t], m)
+            events[-1] = (jump, defer)
+    return out, events
+
+
+def _attn_vmax(width, kind, qkv, n):
+    """[items][heads]: max|v| over the live keys of the KEY item of every item (1 where there is none: such rows are exact zeros)."""
+    heads, hd = attn_heads(width)
+    I = qkv.shape[0]
+    vm = torch.ones(I, heads, dtype=torch.float64)
+    for i in range(I):
+        j = i ^ 1 if kind in (1, 3) else i
+        if int(n[j]) > 0:
+            vm[i] = _attn_split_rows(width, kind, qkv[j, :int(n[j])])[2].double().abs().view(-1, heads, hd).amax(dim=(0, 2))
+    return vm
+
+
+def _attn_item_figures(width, out, ref, vmax, n):
+    """[items]: max over the item's live rows of |out - ref| / max|v| (0 for an item without rows; NaN if the output holds one)."""
+    heads, hd = attn_heads(width)
+    I, nmax = ref.shape[:2]
+    err = (out.double() - ref).abs().view(I, nmax, heads, hd) / vmax[:, None, :, None]
+    return torch.stack([err[i, :int(n[i])].max() if int(n[i]) > 0 else torch.zeros((), dtype=torch.float64) for i in range(I)])
+
+
+def _attn_yardsticks(width, kind, qkv, enc, n, ref, vmax):
+    y = torch.zeros(qkv.shape[0], dtype=torch.float64)
+    for s in range(ATTN_PERMS):
+        o32, _ = _attn_eval(width, kind, qkv, enc, n, torch.float32, perm_seed=s if s else None)
+        y = torch.maximum(y, _attn_item_figures(width, o32, ref, vmax, n))
+    return y
+
+
+GUARD_ROW, GUARD_VALUE = 5, 3000.0
+
+
+@functools.lru_cache(maxsize=8)
+def _attn_inputs(width, kind, items, nmax, family):
+    """items: ((n, seed), ...).  -> qkv [items][nmax][3 width] in the layout of `kind` (NaN in every row at or past n and in the unused third block of
+    kind 1: nothing may read them), enc, n (int32), the fp64 reference, max|v| and the fp32 yardstick per item.
+    family "guard" (fp16x3 range guard): flat, with key row GUARD_ROW of item 0 holding the pair (3000, 3000) in dims 0, 1 of head 0 under a rotation
+    by 45 degrees -> (0, 4243), above 4094 where every unrotated value is below it; item 0's q is 1e-3 of the others' in those two dims, so that the logits
+    stay in the range of `flat`.  In the layout of kind 1 q and k are one block: the pair stands there unrotated."""
+    heads, hd = attn_heads(width)
+    I = len(items)
+    qkv = torch.full((I, nmax, 3 * width), float("nan"))
+    enc = torch.full((I, nmax, hd), float("nan"))
+    for i, (ni, seed) in enumerate(items):
+        q, k, v, e = _attn_item(width, ni, "flat" if family == "guard" else family, seed)
+        if family == "guard" and i == 0:
+            q, k, e = q.clone(), k.clone(), e.clone()
+            q[:, 0:2] *= 1e-3
+            k[GUARD_ROW, 0:2] = GUARD_VALUE
+            e[GUARD_ROW, 0] = e[GUARD_ROW, hd // 2] = 0.5 ** 0.5
+        if kind == 1:   # one block serves as q and as k: the one that carries the ramp
+            q = k
+        qkv[i, :ni] = torch.cat([q, v, torch.full_like(v, float("nan"))] if kind == 1 else [q, k, v], dim=1)
+        enc[i, :ni] = e
+    n = torch.tensor([it[0] for it in items], dtype=torch.int32)
+    ref, events = _attn_eval(width, kind, qkv, enc, n, torch.float64)
+    if family == "ramp":
+        assert any(j for j, _ in events) and any(d for _, d in events), ("ramp: some key tile must force a rescale and some tile must be deferred", events)
+    vmax = _attn_vmax(width, kind, qkv, n)
+    return qkv, enc, n, ref, vmax, _attn_yardsticks(width, kind, qkv, enc, n, ref, vmax)
+
+
+class AttnResult(NamedTuple):
+    out: torch.Tensor          # [items][nmax][width] of the first run (CPU)
+    ref: torch.Tensor          # fp64
+    live: torch.Tensor         # [items][nmax] bool: rows below n[item] of pairs with done == 0
+    n: torch.Tensor
+    figure: float              # max over the live rows of |out - ref| / max|v|
+    yardstick: float           # the fp32 evaluation's figure over the same items
+    untouched: bool            # rows at or past n, rows of stopped pairs and the guard band are still SENTINEL in every run
+    raws: tuple
+
+    @property
+    def repeatable(self):
+        return all(torch.equal(self.raws[0], r) for r in self.raws[1:])
+
+
+def _attn_result(width, bufs, ref, vmax, yard, n, done):
+    I, nmax = ref.shape[:2]
+    raws = tuple(b.cpu() for b in bufs)
+    numel = I * nmax * width
+    running = torch.tensor(done, dtype=torch.int32).repeat_interleave(2) == 0
+    live = (torch.arange(nmax)[None, :] < n[:, None]) & running[:, None]
+    untouched = all(bool((r[numel:] == SENTINEL).all()) and bool((r[:numel].view(I, nmax, width)[~live] == SENTINEL).all()) for r in raws)
+    out = raws[0][:numel].view(I, nmax, width)
+    n_live = torch.where(running, n, torch.zeros_like(n))
+    fig = _attn_item_figures(width, out, ref, vmax, n_live)
+    figure = float("nan") if bool(fig.isnan().any()) else fig.max().item()
+    return AttnResult(out, ref, live, n_live, figure, yard[running].max().item() if bool(running.any()) else 0.0, untouched, raws)
+
+
+def attn_items(ns, seed):
+    return tuple((int(ni), seed * 1000 + i) for i, ni in enumerate(ns))
+
+
+def lg_attention_case(lib, width, kind, items, nmax, nsel, split_items, family, done=None, device="cpu", runs=1):
+    """dim_op_lg_attention_f32 in the arithmetic that is active at the call.  Every run gets a fresh copy of qkv (the fp32 path rotates it in place), a
+    ctx of SENTINEL with a guard band behind it and a workspace of 0xff bytes: a tile image or a partial record that is read before it is written is NaN."""
+    _bind_attention(lib)
+    qkv, enc, n, ref, vmax, yard = _attn_inputs(width, kind, tuple(items), nmax, family)
+    I = len(items)
+    done = [0] * (I // 2) if done is None else list(done)
+    ed, nd, dd = enc.to(device), n.to(device), torch.tensor(done, dtype=torch.int32).to(device)
+    nbytes = int(lib.dim_op_lg_attention_workspace_bytes(width, I, nmax, split_items))
+    bufs = []
+    for _ in range(runs):
+        qd = qkv.to(device, copy=True)
+        ctx = _dense_out(I * nmax * width, device)
+        ws = torch.full((nbytes + 16,), 0xff, dtype=torch.uint8, device=device)
+        rc = lib.dim_op_lg_attention_f32(width, kind, p(qd), p(ed), p(nd), p(dd), p(ctx), I, nmax, nsel, split_items, p(ws), None)
+        assert rc == 0, lib.dim_last_error()
+        _sync(device)
+        bufs.append(ctx)
+    return _attn_result(width, bufs, ref, vmax, yard, n, done)
+
+
+def lg_attention_error(lib, width, kind, device="cpu"):
+    """A (width, kind, arithmetic) that the library does not have: the return code and the message; nothing may be written."""
+    _bind_attention(lib)
+    items = attn_items((40, 40), 1)
+    qkv, enc, n, _, _, _ = _attn_inputs(width, kind, items, 64, "flat")
+    ctx = _dense_out(2 * 64 * width, device)
+    ws = torch.full((int(lib.dim_op_lg_attention_workspace_bytes(width, 2, 64, 0)) + 16,), 0xff, dtype=torch.uint8, device=device)
+    rc = lib.dim_op_lg_attention_f32(width, kind, p(qkv.to(device, copy=True)), p(enc.to(device)), p(n.to(device)),
+                                     p(torch.zeros(1, dtype=torch.int32, device=device)), p(ctx), 2, 64, 64, 0, p(ws), None)
+    _sync(device)
+    return rc, lib.dim_last_error().decode(), bool((ctx.cpu() == SENTINEL).all())
+
+
+def check_attention(r, what=""):
+    """Same bits from every run, nothing written outside the live rows, and the figure (printed first) within ATTN_FACTOR x the fp32 yardstick.
+    -> (figure, yardstick)."""
+    print(f"attention {what}: figure {r.figure:.4g} yardstick {r.yardstick:.4g} bound {ATTN_FACTOR * r.yardstick:.4g} "
+          f"repeatable {r.repeatable} untouched {r.untouched}")
+    assert r.repeatable, "two runs on the same inputs differ"
+    assert r.untouched, "a row at or past n[item], a row of a stopped pair or the guard band was written"
+    assert r.figure <= ATTN_FACTOR * r.yardstick, (r.figure, r.yardstick)
+    return r.figure, r.yardstick
+
+
+# ---- the cases (ids name what they reach) ----
+ATTN_A = dict(ns=(70, 130), nmax=130, nsel=130)                                   # split_items 2 -> 4 parts: item 0's parts 2, 3 empty, part 1 six keys
+ATTN_B = dict(ns=(33, 1, 0, 40, 129, 200, 64, 64), nmax=224, nsel=200)           # one key; no queries; no keys; tile + 1; tile-exact; pair 3 stopped
+ATTN_C_PAIR = ((97, 90001), (130, 90002))                                        # the pair that sits in a 2-item and in a 6-item call
+ATTN_C_NEIGHBOURS = ((130, 90003), (45, 90004), (1, 90005), (64, 90006))
+ATTN_C = dict(nmax=130, nsel=130)
+
+
+def attn_e_counts():
+    """64 ragged counts in 0 .. 100 with 0, 1, 32, 33 and 100 among them."""
+    ns = torch.randint(0, 101, (64,), generator=torch.Generator().manual_seed(64)).tolist()
+    ns[3], ns[10], ns[17], ns[18], ns[40] = 0, 1, 32, 33, 100
+    return tuple(ns)
+
+
+ATTN_E = dict(ns=attn_e_counts(), nmax=100, nsel=100)                              # 4 heads x 64 items = 256 workgroups: two parts
+
+
+def attn_ragged(items, nsel, seed):
+    """`items` counts in 0 .. nsel, the first four pinned to nsel, 0, 1, nsel - 1."""
+    ns = torch.randint(0, nsel + 1, (items,), generator=torch.Generator().manual_seed(seed)).tolist()
+    ns[:4] = [nsel, 0, 1, nsel - 1]
+    return tuple(ns)
+
+
+# hardware only, many resident workgroups: (width, items, nsel, split_items, parts, attention workgroups = query blocks x heads x items x parts)
+ATTN_OCCUPANCY = [(256, 64, 260, 0, 1, 768), (256, 32, 260, 32, 2, 768), (256, 20, 260, 20, 4, 960), (96, 64, 400, 64, 2, 512), (96, 128, 520, 0, 1, 640)]
+
+
+def attn_parts(width, n_items, nsel, split_items):
+    """The launchers' rule (launch_lg_attention_x6 / launch_lgl_attention) -> (parts, attention workgroups)."""
+    wgs = -(-nsel // 128) * attn_heads(width)[0] * n_items
+    parts = (1 if wgs >= 512 else 2 if wgs >= 256 else 4) if 0 < n_items <= split_items else 1
+    return parts, wgs * parts
+
+
+# ---- the fused entry: projection GEMM that writes the K | V images + attention with kv_ready ----
+@functools.lru_cache(maxsize=4)
+def _attn_fused_inputs(kind, items, nmax):
+    """x ~ randn [items][nmax][256] (NaN at or past n), W ~ randn / 16 [256][768 | 512], bias ~ 0.1 randn; the fp64 reference of the WHOLE composition,
+    the fp32 yardstick of the whole composition (fp32 projection, then the fp32 attention), and the fp64 projection rounded to fp32."""
+    I, N = len(items), 768 if kind == 0 else 512
+    g = torch.Generator().manual_seed(7000 + kind)
+    W, bias = (torch.randn(256, N, generator=g) / 16).contiguous(), 0.1 * torch.randn(N, generator=g)
+    x = torch.full((I, nmax, 256), float("nan"))
+    enc = torch.full((I, nmax, 64), float("nan"))
+    for i, (ni, seed) in enumerate(items):
+        gi = torch.Generator().manual_seed(seed)
+        x[i, :ni] = torch.randn(ni, 256, generator=gi)
+        ang = torch.rand(ni, 32, generator=gi) * (2 * torch.pi)
+        enc[i, :ni] = torch.cat([torch.cos(ang), torch.sin(ang)], dim=1)
+    n = torch.tensor([it[0] for it in items], dtype=torch.int32)
+    qkv64 = F.pad(x.double() @ W.double() + bias.double(), (0, 768 - N), value=float("nan"))
+    ref, _ = _attn_eval(256, kind, qkv64, enc, n, torch.float64)
+    vmax = _attn_vmax(256, kind, qkv64, n)
+    qkv32 = F.pad(x @ W + bias, (0, 768 - N), value=float("nan"))
+    yard = torch.zeros(I, dtype=torch.float64)
+    for s in range(ATTN_PERMS):
+        o32, _ = _attn_eval(256, kind, qkv32, enc, n, torch.float32, perm_seed=s if s else None)
+        yard = torch.maximum(yard, _attn_item_figures(256, o32, ref, vmax, n))
+    return x, W, bias, enc, n, ref, vmax, yard, qkv64.float()
+
+
+def lg_qkv_attention_case(lib, kind, items, nmax, nsel, split_items, device="cpu", runs=1):
+    """-> (fused, separate): dim_op_lg_qkv_attention_f32 on (x, W, bias), and dim_op_lg_attention_f32 on the fp64 projection rounded to fp32, both against
+    the fp64 evaluation of the whole composition with the yardstick of the whole composition."""
+    _bind_attention(lib)
+    x, W, bias, enc, n, ref, vmax, yard, qkv_rounded = _attn_fused_inputs(kind, tuple(items), nmax)
+    I, N = len(items), W.shape[1]
+    done = [0] * (I // 2)
+    xd, bd, ed, nd, dd = x.to(device), bias.to(device), enc.to(device), n.to(device), torch.zeros(I // 2, dtype=torch.int32, device=device)
+    nbytes = int(lib.dim_op_lg_attention_workspace_bytes(256, I, nmax, split_items))
+    handle, npad = ctypes.c_void_p(), ctypes.c_int()
+    assert lib.dim_x3_create(p(W), 256, N, ctypes.byref(handle), ctypes.byref(npad)) == 0 and npad.value == N, lib.dim_last_error()
+    fused, separate = [], []
+    try:
+        for _ in range(runs):
+            for bufs in (fused, separate):
+                ctx = _dense_out(I * nmax * 256, device)
+                ws = torch.full((nbytes + 16,), 0xff, dtype=torch.uint8, device=device)
+                if bufs is fused:
+                    qd = torch.full((I, nmax, 768), SENTINEL, device=device)
+                    rc = lib.dim_op_lg_qkv_attention_f32(kind, p(xd), handle, p(bd), p(ed), p(nd), p(dd), p(qd), p(ctx), I, nmax, nsel, split_items, p(ws), None)
+                else:
+                    qd = qkv_rounded.to(device, copy=True)
+                    rc = lib.dim_op_lg_attention_f32(256, kind, p(qd), p(ed), p(nd), p(dd), p(ctx), I, nmax, nsel, split_items, p(ws), None)
+                assert rc == 0, lib.dim_last_error()
+                _sync(device)
+                bufs.append(ctx)
+    finally:
+        lib.dim_x3_destroy(handle)
+    return _attn_result(256, fused, ref, vmax, yard, n, done), _attn_result(256, separate, ref, vmax, yard, n, done)
+
+
+def lg_qkv_attention_unfused_error(lib, device="cpu"):
+    """A shape whose projection GEMM writes no tile images (bf16x6 never does; under fp16x3: 300 rows x 36 items runs the plain 64-row block)."""
+    _bind_attention(lib)
+    I, nmax = 36, 300
+    W = torch.zeros(256, 768)
+    handle, npad = ctypes.c_void_p(), ctypes.c_int()
+    assert lib.dim_x3_create(p(W), 256, 768, ctypes.byref(handle), ctypes.byref(npad)) == 0, lib.dim_last_error()
+    try:
+        z = torch.zeros(16, device=device)
+        zi = torch.zeros(I, dtype=torch.int32, device=device)
+        rc = lib.dim_op_lg_qkv_attention_f32(0, p(z), handle, p(z), p(z), p(zi), p(zi), p(z), p(z), I, nmax, nmax, 0, p(z), None)
+    finally:
+        lib.dim_x3_destroy(handle)
+    return rc, lib.dim_last_error().decode()
+
+
+def saturation_op_count(lib, reset=False):
+    """The DIM_SAT_OP counter (site 7 of include/dim_hip.h) through dim_saturation_read."""
+    counts, total = (ctypes.c_uint * 16)(), ctypes.c_ulonglong()
+    assert lib.dim_saturation_read(counts, ctypes.byref(total), int(reset), None) == 0, lib.dim_last_error()
+    return int(counts[7])
+
+
+# (width, kind, arithmetic = dim_tune_set key 1) that exist / that the library refuses: SuperGlue and width 96 have no fp32 form
+ATTN_VARIANTS = [(256, k, m) for k in range(4) for m in (2, 1, 0) if not (k >= 2 and m == 0)] + [(96, k, m) for k in (0, 1) for m in (2, 1)]
+ATTN_REFUSED = [(256, 2, 0), (256, 3, 0), (96, 0, 0), (96, 1, 0)]
+ATTN_MODE_NAMES = {2: "fp16x3", 1: "bf16x6", 0: "fp32"}
+ATTN_KIND_NAMES = ("self", "cross", "sg_self", "sg_cross")
+
+
+def attn_variant_id(v):
+    return f"w{v[0]}-{ATTN_KIND_NAMES[v[1]]}-{ATTN_MODE_NAMES[v[2]]}"
+
+
+def attn_case_a(lib, width, kind, split_items, family, device="cpu", runs=2):
+    return lg_attention_case(lib, width, kind, attn_items(ATTN_A["ns"], 1), ATTN_A["nmax"], ATTN_A["nsel"], split_items, family, device=device, runs=runs)
+
+
+def attn_case_b(lib, width, kind, done3, split_items, device="cpu", runs=2):
+    """Case B with done = (0, 0, 0, done3); besides the result, the exact-zero check of the empty key set: under kind 1 / 3 item 3 (40 rows) reads the keys
+    of item 2, which has none (under kind 0 / 2 the item without keys has no queries either)."""
+    r = lg_attention_case(lib, width, kind, attn_items(ATTN_B["ns"], 2), ATTN_B["nmax"], ATTN_B["nsel"], split_items, "flat", done=(0, 0, 0, done3),
+                          device=device, runs=runs)
+    assert not bool(r.live[6:].any()) and int(r.live.sum()) == sum(ATTN_B["ns"][:6])
+    if kind in (1, 3):
+        assert bool((r.out[3, :40] == 0.0).all()), "the rows of an item whose key set is empty are not exact zeros"
+        assert not bool((r.out[1, :1] == 0.0).all())          # (item 1 reads item 0's 33 keys)
+    return r
+
+
+def attn_case_c(lib, width, kind, device="cpu", runs=2):
+    """-> (the pair alone, the pair as items 4, 5 of a 6-item call), both with the key range in 4 parts."""
+    alone = lg_attention_case(lib, width, kind, ATTN_C_PAIR, ATTN_C["nmax"], ATTN_C["nsel"], 2, "ramp", device=device, runs=runs)
+    among = lg_attention_case(lib, width, kind, ATTN_C_NEIGHBOURS + ATTN_C_PAIR, ATTN_C["nmax"], ATTN_C["nsel"], 6, "ramp", device=device, runs=runs)
+    assert attn_parts(width, 2, ATTN_C["nsel"], 2)[0] == 4 and attn_parts(width, 6, ATTN_C["nsel"], 6)[0] == 4
+    return alone, among
+
+
+def attn_case_e(lib, kind, device="cpu", runs=2):
+    assert attn_parts(256, 64, ATTN_E["nsel"], 64) == (2, 512)
+    return lg_attention_case(lib, 256, kind, attn_items(ATTN_E["ns"], 3), ATTN_E["nmax"], ATTN_E["nsel"], 64, "ramp", device=device, runs=runs)
+
+
+def attn_case_guard(lib, kind, device="cpu", runs=1):
+    """-> (result, DIM_SAT_OP count of the call) on the `guard` inputs (see _attn_inputs); the counter is cleared before and after."""
+    saturation_op_count(lib, reset=True)
+    r = lg_attention_case(lib, 256, kind, attn_items((40, 40), 4), 64, 40, 0, "guard", device=device, runs=runs)
+    return r, saturation_op_count(lib, reset=True)
+
+
+def attn_case_occupancy(lib, width, kind, items, nsel, split_items, parts, wgs, device="cuda", runs=2):
+    assert attn_parts(width, items, nsel, split_items) == (parts, wgs)
+    ns = attn_ragged(items, nsel, items + nsel)
+    return lg_attention_case(lib, width, kind, attn_items(ns, 5), nsel, nsel, split_items, "ramp", device=device, runs=runs)

@@ -64,6 +64,16 @@ Case -> kernel (from launch_gemm / launch_gemm_x6 / launch_gemm_x6_nt / launch_c
   test_select_topk_reused_workspace           three calls on one workspace: chunked (2 chunks) -> chunked, sparse + fill -> topk_kernel
   test_sample_descriptors                     sample_desc_kernel, one wave per keypoint: 5x7 (16 x 3 wg), 12x20 (75 x 2 wg), 128x128 (512 x 2 = 1024 wg)
 
+  tests/test_attention_ops_gpu.py (dim_op_lg_attention_f32 / dim_op_lg_qkv_attention_f32; MODE 2 = fp16x3, 1 = bf16x6; wg of the attention kernel, surplus
+  workgroups of its XCD-rounded 1-D grid included; the full table with the merge kernels' grids is in that file's docstring)
+    small_ragged (A)  2 items, n (70, 130)          attn_kernel 16 wg | kv_prep_kernel<MODE> + attn_x6_kernel<MODE> 16 wg, 64 wg + attn_combine_kernel<4> |
+                                                   kv_prep96_kernel<MODE> + attn_d96_kernel<MODE> 16 wg, 64 wg + attn_combine96_kernel
+    edge_counts (B)   8 items, nsel 200 < nmax 224  attn_kernel 64 wg | attn_x6_kernel<MODE> 256 wg + attn_combine_kernel<4>, 64 wg | attn_d96_kernel<MODE> 64 wg + combine96, 16 wg
+    neighbours (C)    2 | 6 items, four parts       attn_x6_kernel<MODE> 64 | 192 wg, attn_d96_kernel<MODE> 64 | 64 wg
+    fused (D)         2 items, nsel 130             gemm_x6_qkv_small_kernel<64,true,256> 60 | 40 wg + attn_x6_kernel<2> with kv_ready
+    two_parts (E)     64 items, nsel 100            attn_x6_kernel<MODE> 512 wg + attn_combine_kernel<2>
+    many_resident     256: 64 x 260 768 wg (1 part), 32 x 260 768 wg (2 parts), 20 x 260 960 wg (4 parts); 96: 64 x 400 512 wg (2 parts), 128 x 520 640 wg (1 part)
+
 launch_gemm_x6's gemm_x6_kernel<2,64,2,2> branch is not in the table: a small problem has cdiv(M,128) * cdiv(N,128) < 256 workgroups, so at most
 2 * 255 = 510 workgroups of 64 rows, which is never above the 512 that the branch before it accepts.
 """
