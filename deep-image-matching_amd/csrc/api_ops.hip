@@ -459,6 +459,106 @@ int dim_op_lg_qkv_attention_f32(int kind, const float* x, const void* w_x3, cons
   return launch_lg_attention(st, kind, s, 1);
 }
 
+// LightGlue / LighterGlue confidence, decision, pruning, assignment and finalize as the matchers run them (lg_api.hip, lgl_api.hip): an LgState over the
+// caller's tensors, then the matchers' own launchers.  `need` names the pointers the entry uses; the others stay as the caller gave them.
+namespace {
+enum : unsigned {
+  HS_DESC = 1u << 0, HS_ENC = 1u << 1, HS_SIM = 1u << 2, HS_CONF = 1u << 3, HS_MTCH = 1u << 4, HS_ZLS = 1u << 5, HS_RMAX = 1u << 6, HS_RLSE = 1u << 7,
+  HS_BEST = 1u << 8, HS_ARG = 1u << 9, HS_NCUR = 1u << 10, HS_NNEW = 1u << 11, HS_NORIG = 1u << 12, HS_IND = 1u << 13, HS_DEST = 1u << 14,
+  HS_PRUNE = 1u << 15, HS_DONE = 1u << 16, HS_CNT = 1u << 17
+};
+int lg_head_state(LgState& st, const char* who, const dim_lg_head_state* hs, unsigned need) {
+  DIM_REQUIRE(hs != nullptr, "%s: null state", who);
+  DIM_REQUIRE(hs->width == 256 || hs->width == 96, "%s: width %d (256: LightGlue; 96: LighterGlue)", who, hs->width);
+  DIM_REQUIRE(hs->n_pairs > 0 && hs->nmax > 0 && hs->nsel > 0 && hs->nsel <= hs->nmax, "%s: need n_pairs %d > 0 and 0 < nsel %d <= nmax %d", who,
+              hs->n_pairs, hs->nsel, hs->nmax);
+  DIM_REQUIRE((long long)hs->n_pairs * 2 * hs->nmax * 256 <= 0x7fffffffLL, "%s: %d pairs of %d rows exceed 2^31 elements", who, hs->n_pairs, hs->nmax);
+  const void* ptr[18] = {hs->desc, hs->enc, hs->sim, hs->conf, hs->mtch, hs->zls, hs->rmax, hs->rlse, hs->best, hs->arg, hs->n_cur, hs->n_new,
+                         hs->n_orig, hs->ind, hs->dest, hs->prune, hs->done, hs->cnt_lt};
+  static const char* const name[18] = {"desc", "enc", "sim", "conf", "mtch", "zls", "rmax", "rlse", "best", "arg", "n_cur", "n_new",
+                                       "n_orig", "ind", "dest", "prune", "done", "cnt_lt"};
+  for (int i = 0; i < 18; ++i) DIM_REQUIRE(!((need >> i) & 1u) || ptr[i] != nullptr, "%s: null %s", who, name[i]);
+  st.n_pairs = hs->n_pairs; st.n_items = 2 * hs->n_pairs; st.nmax = hs->nmax; st.nsel = hs->nsel;
+  st.desc = hs->desc; st.enc = hs->enc; st.sim = hs->sim; st.conf = hs->conf; st.mtch = hs->mtch; st.zls = hs->zls; st.rmax = hs->rmax;
+  st.rlse = hs->rlse; st.best = hs->best; st.arg = (int*)hs->arg; st.n_cur = (int*)hs->n_cur; st.n_new = (int*)hs->n_new; st.n_orig = (int*)hs->n_orig;
+  st.ind = (int*)hs->ind; st.dest = (int*)hs->dest; st.prune = (int*)hs->prune; st.done = (int*)hs->done; st.cnt_lt = (int*)hs->cnt_lt;
+  if (hs->width == 96) { st.dim = 96; st.heads = 1; st.head_dim = 96; }
+  return 0;
+}
+struct LgPruneWs {
+  size_t tdesc, tenc, tind, total;   // byte offsets
+};
+LgPruneWs lg_prune_ws(int width, int n_items, int nmax) {
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t rows = (size_t)n_items * nmax;
+  LgPruneWs w;
+  w.tdesc = 0;
+  w.tenc = w.tdesc + up(rows * width * sizeof(float));
+  w.tind = w.tenc + up(rows * (width == 256 ? 64 : 96) * sizeof(float));
+  w.total = w.tind + up(rows * sizeof(int));
+  return w;
+}
+}  // namespace
+
+int dim_op_lg_confidence_f32(const dim_lg_head_state* hs, const float* w_tok, const float* b_tok, const float* w_match, const float* b_match, float thr,
+                             int use_token, void* stream) {
+  const char* who = "dim_op_lg_confidence_f32";
+  LgState st{};
+  int rc = lg_head_state(st, who, hs, HS_DESC | HS_CONF | HS_MTCH | HS_CNT | HS_NCUR | HS_DONE);
+  if (rc != 0) return rc;
+  DIM_REQUIRE(w_match && b_match && (!use_token || (w_tok && b_tok)), "%s: null weights", who);
+  if (hs->width == 96) return launch_lgl_confidence(st, w_tok, b_tok, w_match, b_match, thr, use_token ? 1 : 0, (hipStream_t)stream);
+  return launch_lg_confidence(st, w_tok, b_tok, w_match, b_match, thr, use_token ? 1 : 0, (hipStream_t)stream);
+}
+
+int dim_op_lg_decide(const dim_lg_head_state* hs, int layer, float depth_conf, int early, int last, void* stream) {
+  const char* who = "dim_op_lg_decide";
+  LgState st{};
+  int rc = lg_head_state(st, who, hs, HS_DONE | HS_CNT | HS_NORIG);
+  if (rc != 0) return rc;
+  DIM_REQUIRE(layer >= 0, "%s: layer %d", who, layer);
+  return launch_lg_decide(st, layer, depth_conf, early ? 1 : 0, last ? 1 : 0, (hipStream_t)stream, nullptr);
+}
+
+size_t dim_op_lg_prune_workspace_bytes(int width, int n_items, int nmax) {
+  if ((width != 256 && width != 96) || n_items <= 0 || nmax <= 0) return 0;
+  return lg_prune_ws(width, n_items, nmax).total;
+}
+
+int dim_op_lg_prune(const dim_lg_head_state* hs, int layer, double width_conf, float thr, int use_token, int pruning_min, void* workspace, void* stream) {
+  const char* who = "dim_op_lg_prune";
+  LgState st{};
+  int rc = lg_head_state(st, who, hs, HS_DESC | HS_ENC | HS_CONF | HS_MTCH | HS_NCUR | HS_NNEW | HS_IND | HS_DEST | HS_PRUNE | HS_DONE);
+  if (rc != 0) return rc;
+  DIM_REQUIRE(workspace && layer >= 0, "%s: null workspace, or layer %d", who, layer);
+  const LgPruneWs w = lg_prune_ws(hs->width, st.n_items, st.nmax);
+  char* base = (char*)workspace;
+  st.tdesc = (float*)(base + w.tdesc); st.tenc = (float*)(base + w.tenc); st.tind = (int*)(base + w.tind);
+  return launch_lg_prune(st, layer, width_conf, thr, use_token ? 1 : 0, pruning_min, (hipStream_t)stream);
+}
+
+int dim_op_lg_assign_f32(const dim_lg_head_state* hs, int tag, const float* w_match, const float* b_match, float* dense, void* stream) {
+  const char* who = "dim_op_lg_assign_f32";
+  LgState st{};
+  int rc = lg_head_state(st, who, hs, HS_DESC | HS_SIM | HS_ZLS | HS_RMAX | HS_RLSE | HS_BEST | HS_ARG | HS_NCUR | HS_DONE);
+  if (rc != 0) return rc;
+  DIM_REQUIRE(w_match && b_match && tag >= 0, "%s: null weights, or tag %d < 0", who, tag);
+  rc = launch_lg_assign_stats(st, tag, w_match, b_match, (hipStream_t)stream);
+  if (rc != 0) return rc;
+  return launch_lg_assign_argmax(st, tag, dense, (hipStream_t)stream);
+}
+
+int dim_op_lg_finalize(const dim_lg_head_state* hs, int n_layers, int prune_enabled, float filter_thr, int out_cap, int64_t* matches, float* mscores,
+                       int32_t* n_matches, int32_t* mfull, float* msfull, int32_t* stop, int32_t* prune_out, void* stream) {
+  const char* who = "dim_op_lg_finalize";
+  LgState st{};
+  int rc = lg_head_state(st, who, hs, HS_BEST | HS_ARG | HS_NCUR | HS_NORIG | HS_IND | HS_DONE | (prune_enabled ? HS_PRUNE : 0u));
+  if (rc != 0) return rc;
+  DIM_REQUIRE(matches && mscores && n_matches && mfull && msfull && stop && prune_out && out_cap > 0, "%s: null output, or out_cap %d", who, out_cap);
+  return launch_lg_finalize(st, n_layers, prune_enabled ? 1 : 0, filter_thr, out_cap, (long long*)matches, mscores, (int*)n_matches, (int*)mfull, msfull,
+                            (int*)stop, (int*)prune_out, (hipStream_t)stream);
+}
+
 int dim_convx6_create(const float* w_oihw_host, int cin, int cout, void** out_dev) {
   DIM_REQUIRE(w_oihw_host && out_dev && (cin == 64 || cin == 128) && cout % 64 == 0, "dim_convx6_create: bad argument");
   const int mode = g_precision_mode == 1 ? 1 : 2;

@@ -345,6 +345,8 @@ __device__ __forceinline__ float lg_score(float sim, float rm, float rl, float c
   return (((sim - rm) - rl) + ((sim - cm) - cl)) + (z0 + z1);
 }
 // row argmax (first maximal index, Tensor.max on CPU) — wave per row; optionally dumps the dense matrix.
+// The index sentinel 0x7fffffff of the four argmax kernels (these two and the 16-byte forms below) survives where no score compares greater than -inf,
+// i.e. in a row or column of NaNs.  Rule: an arg outside the other side's [0, n_cur) means "no match"; lg_finalize_kernel reads nothing through it.
 __global__ __launch_bounds__(256) void lg_row_argmax_kernel(LgState st, int tag, float* __restrict__ dense) {
   const int p = blockIdx.y;
   const int dn = st.done[p];
@@ -430,13 +432,16 @@ __global__ __launch_bounds__(1024) void lg_finalize_kernel(LgState st, int n_lay
   }
   __syncthreads();
   const int m = st.n_cur[2 * p], n = st.n_cur[2 * p + 1];
+  // An arg outside [0, n) on side 0 / [0, m) on side 1 means "no match" for that row / column and nothing is read through it: the argmax kernels start
+  // from the index 0x7fffffff and keep it where no score compares greater than -inf (a row of NaNs has no maximum; the range guard counts a NaN
+  // descriptor, but the call runs on).  Match index -1 and score 0, as for a row that is not mutual.
   // side 0
   const int per = (m + 1023) / 1024;
   const int i0 = t * per, i1 = min(i0 + per, m);
   int cnt = 0;
   for (int i = i0; i < i1; ++i) {
     const int j = st.arg[b0 + i];
-    const bool mutual = st.arg[b1 + j] == i;
+    const bool mutual = (unsigned)j < (unsigned)n && st.arg[b1 + j] == i;
     const float ms = mutual ? expf(st.best[b0 + i]) : 0.0f;
     const bool valid = mutual && ms > filter_thr;
     const int oi = st.ind[b0 + i];
@@ -455,7 +460,7 @@ __global__ __launch_bounds__(1024) void lg_finalize_kernel(LgState st, int n_lay
   int run = part[t] - cnt;
   for (int i = i0; i < i1; ++i) {
     const int j = st.arg[b0 + i];
-    const bool mutual = st.arg[b1 + j] == i;
+    const bool mutual = (unsigned)j < (unsigned)n && st.arg[b1 + j] == i;
     const float ms = mutual ? expf(st.best[b0 + i]) : 0.0f;
     if (mutual && ms > filter_thr) {
       if (run < out_cap) {
@@ -470,7 +475,7 @@ __global__ __launch_bounds__(1024) void lg_finalize_kernel(LgState st, int n_lay
   // side 1 (LGN:292,295)
   for (int j = t; j < n; j += 1024) {
     const int i = st.arg[b1 + j];
-    const bool mutual1 = st.arg[b0 + i] == j;
+    const bool mutual1 = (unsigned)i < (unsigned)m && st.arg[b0 + i] == j;
     const bool mutual0 = mutual1;  // arg0[i] == j and arg1[j] == i are the same condition seen from j
     const float ms0 = mutual0 ? expf(st.best[b0 + i]) : 0.0f;
     const bool valid1 = mutual1 && (ms0 > filter_thr);

@@ -575,6 +575,62 @@ int dim_op_lg_qkv_attention_f32(int kind, const float* x, const void* w_x3_handl
                                 const int32_t* done_dev, float* qkv, float* ctx, int n_items, int nmax, int nsel, int split_items, void* workspace,
                                 void* stream);
 
+/* What turns the LightGlue / LighterGlue network output into the integers a caller sees (csrc/lg_kernels.hip, the 96-wide forms in lgl_kernels.hip):
+ * token confidence and the early-stop decision, point pruning, the double-softmax assignment, mutual-argmax filtering with the scatter back to the
+ * un-pruned index space.  Each entry fills the matchers' state over the caller's device tensors and calls the matchers' own launcher; an entry checks
+ * the pointers it uses (named with it below) and leaves the others alone, so they may be NULL.  item = 2 * pair + side.  Everything is ragged: rows at
+ * or past n_cur[item] are neither read nor written, and a pair is skipped unless its done flag selects it.
+ *   width 256 | 96: desc rows of `width` floats, enc rows of 64 | 96 (cos | sin).  Launch shapes follow nsel (n_cur[item] <= nsel <= nmax), strides nmax. */
+typedef struct dim_lg_head_state {
+  int32_t width, n_pairs, nmax, nsel;
+  float* desc;      /* [items][nmax][width] */
+  float* enc;       /* [items][nmax][64 | 96] */
+  float* sim;       /* [pairs][nmax][nmax]: similarity of row (side 0 point) x column (side 1 point) */
+  float* conf;      /* [items][nmax] token confidence */
+  float* mtch;      /* [items][nmax] matchability (sigmoid) */
+  float* zls;       /* [items][nmax] logsigmoid of the matchability logit */
+  float* rmax;      /* [items][nmax] maximum ... */
+  float* rlse;      /* [items][nmax] ... and log of the sum of exp(sim - maximum) of a row (side 0) / a column (side 1) */
+  float* best;      /* [items][nmax] best log-assignment per row / column */
+  int32_t* arg;     /* [items][nmax] its index: the column of a row (side 0), the row of a column (side 1); the first one among equals */
+  int32_t* n_cur;   /* [items] live points */
+  int32_t* n_new;   /* [items] live points after the pruning pass */
+  int32_t* n_orig;  /* [items] points before any pruning */
+  int32_t* ind;     /* [items][nmax] original index of each live point */
+  int32_t* dest;    /* [items][nmax] where the pruning pass moves a live point (-1: dropped) */
+  int32_t* prune;   /* [items][nmax] layers survived, by ORIGINAL index */
+  int32_t* done;    /* [pairs] 0 running, > 0 stopped at that layer, < 0 left without keypoints */
+  int32_t* cnt_lt;  /* [pairs] points of the pair with confidence < threshold */
+} dim_lg_head_state;
+/* conf = sigmoid(desc . w_tok + b_tok) (0 when !use_token), mtch = sigmoid(desc . w_match + b_match) per live point of the running pairs (done == 0);
+ * cnt_lt[pair] += the number of its points with conf < thr (use_token only).  Uses desc, conf, mtch, cnt_lt, n_cur, done. */
+int dim_op_lg_confidence_f32(const dim_lg_head_state* hs, const float* w_tok, const float* b_tok, const float* w_match, const float* b_match, float thr,
+                             int use_token, void* stream);
+/* Per running pair: last -> done = layer + 1; else early and 1 - cnt_lt / (n_orig[0] + n_orig[1]) > depth_conf -> done = layer + 1.  cnt_lt of every
+ * pair returns to 0; a stopped pair keeps its layer.  Uses done, cnt_lt, n_orig. */
+int dim_op_lg_decide(const dim_lg_head_state* hs, int layer, float depth_conf, int early, int last, void* stream);
+/* Pruning of the running pairs' items with n_cur > pruning_min: a point stays if mtch > 1 - width_conf (compared in fp32) or, with use_token,
+ * conf <= thr.  dest and n_new are written; the kept rows of desc, enc and ind move to the front in order; prune[ind] += 1 for every kept point; n_cur =
+ * n_new; a side pruned to nothing sets done = -(layer + 2).  When nothing goes on a side, its rows and the workspace are not touched.  Uses desc, enc,
+ * conf, mtch, n_cur, n_new, ind, dest, prune, done.  workspace: dim_op_lg_prune_workspace_bytes(...) bytes, 16-byte aligned. */
+size_t dim_op_lg_prune_workspace_bytes(int width, int n_items, int nmax);
+int dim_op_lg_prune(const dim_lg_head_state* hs, int layer, double width_conf, float thr, int use_token, int pruning_min, void* workspace, void* stream);
+/* The log-assignment of LightGlue (LGN:246-275) on a caller-supplied similarity, for the pairs with done == tag (tag > 0; w_match [width], b_match [1])
+ * or, tag == 0, every pair with done > 0 (w_match [layers][width], b_match [layers], row done - 1):
+ *   score(i, j) = log_softmax(sim, columns)(i, j) + log_softmax(sim, rows)(i, j) + logsigmoid(z0[i]) + logsigmoid(z1[j]),  z = desc . w_match + b_match.
+ * Writes zls, rmax, rlse, best, arg (both sides) and, if dense is not NULL, score into dense [pairs][nmax + 1][nmax + 1] (live entries only).
+ * Which kernels run follows nmax and nsel as in the matchers: the 16-byte kernels when nmax is a multiple of 4 and nsel <= 4096 (rows held in 8
+ * registers per lane up to nsel 2048, 16 above), the generic ones otherwise.  Uses desc, sim, zls, rmax, rlse, best, arg, n_cur, done. */
+int dim_op_lg_assign_f32(const dim_lg_head_state* hs, int tag, const float* w_match, const float* b_match, float* dense, void* stream);
+/* LightGlue's filter_matches (LGN:281-297) and the scatter through ind (LGN:543-566), one pair per workgroup.  Row i and column j match when
+ * arg0[i] == j and arg1[j] == i; the match is valid when exp(best0[i]) > filter_thr.  An arg outside [0, n_cur of the other side) means "no match".
+ *   matches [pairs][out_cap][2] (int64), mscores [pairs][out_cap]: the valid matches in row order as ORIGINAL indices, the first out_cap of them;
+ *   n_matches [pairs] = min(count, out_cap);  mfull [items][nmax] (-1: none), msfull [items][nmax] (0 unless mutual): by original index, complete;
+ *   stop [pairs] = |done|;  prune_out [items][nmax] = prune (prune_enabled) or n_layers below n_orig, 0 above.  A pair with done <= 0 has no matches.
+ * Uses best, arg, n_cur, n_orig, ind, prune, done. */
+int dim_op_lg_finalize(const dim_lg_head_state* hs, int n_layers, int prune_enabled, float filter_thr, int out_cap, int64_t* matches, float* mscores,
+                       int32_t* n_matches, int32_t* mfull, float* msfull, int32_t* stop, int32_t* prune_out, void* stream);
+
 /* 3x3/s1/p1 conv, NHWC fp32, weights [9][cin][cout], bias+ReLU and optional
  * 2x2 max-pool fused (SPN:161-171).  cin in {64,128}, cout % 64 == 0. */
 int dim_op_conv3x3_nhwc_f32(const float* in, const float* w_tap_cin_cout, const float* bias, float* out, int batch,

@@ -1171,3 +1171,680 @@ def attn_case_occupancy(lib, width, kind, items, nsel, split_items, parts, wgs, 
     assert attn_parts(width, items, nsel, split_items) == (parts, wgs)
     ns = attn_ragged(items, nsel, items + nsel)
     return lg_attention_case(lib, width, kind, attn_items(ns, 5), nsel, nsel, split_items, "ramp", device=device, runs=runs)
+
+
+# ---------------------------------------------------------------------------------------------------------------- LightGlue head: confidence, decide, prune, assign, finalize
+# dim_op_lg_confidence_f32 / dim_op_lg_decide / dim_op_lg_prune / dim_op_lg_assign_f32 / dim_op_lg_finalize (include/dim_hip.h) = the launchers of
+# csrc/lg_kernels.hip (96-wide forms: lgl_kernels.hip) over caller tensors.  References: plain torch in fp64 on the CPU, written from the operation.
+#   floating-point outputs   figure = max |out - fp64| over the live entries, yardstick = the same figure of an fp32 torch evaluation of the same formula
+#                            (largest of HEAD_PERMS row / column / channel orders), bound = HEAD_FACTOR x yardstick.  Match scores exp(best): 2 ulp (below).
+#   integer outputs          exact, every entry.  The builders assert on the fp64 reference that every decision has a margin of HEAD_MARGIN x the bound
+#                            (top-two gaps, exp(best) against the filter threshold, conf / mtch against their thresholds); a seed that does not is skipped.
+# Every buffer an op writes starts as 0xff bytes (NaN / -1) with a guard band of GUARD_ELEMS behind it; rows at or past n_cur hold NaN in every input.
+HEAD_FACTOR, HEAD_PERMS, HEAD_MARGIN = 2.0, 4, 16.0
+HEAD_PTRS = ("desc", "enc", "sim", "conf", "mtch", "zls", "rmax", "rlse", "best", "arg", "n_cur", "n_new", "n_orig", "ind", "dest", "prune", "done", "cnt_lt")
+HEAD_LAYERS = 9
+ARG_NONE = 0x7fffffff
+
+
+class LgHeadState(ctypes.Structure):
+    _fields_ = [("width", _ci), ("n_pairs", _ci), ("nmax", _ci), ("nsel", _ci)] + [(k, _vp) for k in HEAD_PTRS]
+
+
+def _bind_head(lib):
+    sp, cf = ctypes.POINTER(LgHeadState), ctypes.c_float
+    lib.dim_op_lg_confidence_f32.argtypes = [sp, _vp, _vp, _vp, _vp, cf, _ci, _vp]
+    lib.dim_op_lg_decide.argtypes = [sp, _ci, cf, _ci, _ci, _vp]
+    lib.dim_op_lg_prune_workspace_bytes.argtypes = [_ci, _ci, _ci]
+    lib.dim_op_lg_prune_workspace_bytes.restype = ctypes.c_size_t
+    lib.dim_op_lg_prune.argtypes = [sp, _ci, ctypes.c_double, cf, _ci, _ci, _vp, _vp]
+    lib.dim_op_lg_assign_f32.argtypes = [sp, _ci, _vp, _vp, _vp, _vp]
+    lib.dim_op_lg_finalize.argtypes = [sp, _ci, _ci, cf, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    for f in (lib.dim_op_lg_confidence_f32, lib.dim_op_lg_decide, lib.dim_op_lg_prune, lib.dim_op_lg_assign_f32, lib.dim_op_lg_finalize):
+        f.restype = _ci
+
+
+def _head_state(width, n_pairs, nmax, nsel, **tensors):
+    hs = LgHeadState(width, n_pairs, nmax, nsel)
+    for k, t in tensors.items():
+        assert k in HEAD_PTRS
+        setattr(hs, k, t.data_ptr())
+    return hs
+
+
+def _filled(numel, dtype, device, fill=0xff):
+    """numel + GUARD_ELEMS elements of `dtype`, every byte `fill`."""
+    item = torch.empty((), dtype=dtype).element_size()
+    return torch.full(((numel + GUARD_ELEMS) * item,), fill, dtype=torch.uint8, device=device).view(dtype)
+
+
+def _guarded(t, device, fill=0xff):
+    """An in / out tensor: its values, flat, with the guard band behind them."""
+    out = _filled(t.numel(), t.dtype, "cpu", fill)
+    out[:t.numel()] = t.contiguous().view(-1)
+    return out.to(device)
+
+
+def _is_fill(flat, fill=0xff):
+    """flat (CPU, 1-D) -> bool per element: every byte still holds `fill`."""
+    return (flat.contiguous().view(torch.uint8).view(flat.numel(), flat.element_size()) == fill).all(dim=1)
+
+
+def _same_bits(raws):
+    return all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for r in raws[1:] for a, b in zip(raws[0], r))
+
+
+def _first_argmax(x, dim):
+    """(max, the LOWEST index that holds it) along dim — Tensor.max on the CPU, spelled out."""
+    best = x.amax(dim=dim)
+    idx = torch.arange(x.shape[dim]).view(-1, 1) if dim == 0 else torch.arange(x.shape[dim]).view(1, -1)
+    return best, torch.where(x == best.unsqueeze(dim), idx, x.shape[dim]).amin(dim=dim)
+
+
+@functools.lru_cache(maxsize=None)
+def head_weights(width):
+    """[HEAD_LAYERS][width] weight rows ~ randn / sqrt(width) (logits ~ N(0, 1) on randn descriptors) and biases ~ 0.3 randn, for the token and the
+    matchability heads."""
+    g = torch.Generator().manual_seed(4242 + width)
+    return (torch.randn(HEAD_LAYERS, width, generator=g) / width ** 0.5, 0.3 * torch.randn(HEAD_LAYERS, generator=g),
+            torch.randn(HEAD_LAYERS, width, generator=g) / width ** 0.5, 0.3 * torch.randn(HEAD_LAYERS, generator=g))
+
+
+# ---- assignment ----
+ASSIGN_THR = 0.1
+TIE_ROWS = (5, 76)                                    # row groups 5 and 12 of both column kernels (64 and 16 groups)
+TIE_COLS = {"lanes": (9, 70), "float4": (8, 10), "lane": (9, 73), "lane16": (9, 265)}   # 16-byte kernels: lane = (j / 4) % 64; generic: j % 64
+
+
+def _assign_eval(sim, d0, d1, w, b, dtype):
+    """LightGlue's log assignment (LGN:246-275) in `dtype`: -> zls0, zls1, lse0 (rows), lse1 (columns), score."""
+    sim, d0, d1, w, b = sim.to(dtype), d0.to(dtype), d1.to(dtype), w.to(dtype), b.to(dtype)
+    z0, z1 = F.logsigmoid(d0 @ w + b), F.logsigmoid(d1 @ w + b)
+    score = F.log_softmax(sim, dim=1) + F.log_softmax(sim, dim=0) + z0[:, None] + z1[None, :]
+    return z0, z1, torch.logsumexp(sim, dim=1), torch.logsumexp(sim, dim=0), score
+
+
+class AssignPair(NamedTuple):
+    sim: torch.Tensor      # [m][n] fp32
+    d0: torch.Tensor       # [m][width]
+    d1: torch.Tensor
+    ref: dict              # fp64: zls0, zls1, lse0, lse1, score, best0, best1, arg0, arg1
+    yard: dict             # zls, lse, best, dense -> the fp32 evaluation's figure
+    seed: int
+
+
+def _assign_errors(out, ref):
+    """out / ref: (zls0, zls1, lse0, lse1, best0, best1, score) -> {zls, lse, best, dense}: max |out - ref|."""
+    e = [(o.double() - r).abs().max().item() if r.numel() else 0.0 for o, r in zip(out, ref)]
+    return {"zls": max(e[0], e[1]), "lse": max(e[2], e[3]), "best": max(e[4], e[5]), "dense": e[6]}
+
+
+def _assign_try(width, m, n, family, ties, wrow, seed):
+    g = torch.Generator().manual_seed(seed)
+    _, _, W, B = head_weights(width)
+    w, b = W[wrow], B[wrow]
+    d0, d1 = torch.randn(m, width, generator=g), torch.randn(n, width, generator=g)
+    rows, cols = torch.arange(m), torch.arange(n)
+    if family == "ramp":   # + 5 per group of 64 rows (the stride of a thread of lg_col_stats4_kernel), centred; one column per row lifted by 3: a clear row maximum
+        sim = 0.25 * torch.randn(m, n, generator=g) + 5.0 * (rows // 64)[:, None] - 2.5 * ((m - 1) // 64)
+        sim[rows, torch.randint(0, n, (m,), generator=g)] += 3.0
+    else:
+        sim = 3.0 * torch.randn(m, n, generator=g)
+    planted = None
+    if family == "planted":
+        k = max(1, round(0.6 * min(m, n)))
+        pr, pc = torch.randperm(m, generator=g)[:k], torch.randperm(n, generator=g)[:k]
+        sim[pr, pc] += 12.0
+        for d, idx in ((d0, pr), (d1, pc)):   # matchability logits 1 .. 4 on the planted points
+            d[idx] += ((1.0 + 3.0 * torch.rand(k, generator=g) - (d[idx] @ w + b)) / (w @ w))[:, None] * w
+        planted = (pr, pc)
+    keep_r, keep_c = torch.ones(m, dtype=torch.bool), torch.ones(n, dtype=torch.bool)
+    tie_c = tie_r = None
+    if ties:
+        ca, cb = TIE_COLS[ties] if n > TIE_COLS[ties][1] else TIE_COLS["float4"]   # (a side of 37 columns: the pair inside one float4)
+        sim[3:9, ca] += 15.0                      # rows whose maximum is the tied column
+        if m > TIE_ROWS[1]:
+            tie_r = TIE_ROWS
+            sim[tie_r[0], 20:26] += 15.0          # columns whose maximum is the tied row
+        sim[:, cb], d1[cb], keep_c[cb], tie_c = sim[:, ca], d1[ca], False, (ca, cb)
+        if tie_r:
+            sim[tie_r[1]], d0[tie_r[1]], keep_r[tie_r[1]] = sim[tie_r[0]], d0[tie_r[0]], False
+    z0, z1, l0, l1, score = _assign_eval(sim, d0, d1, w, b, torch.float64)
+    best0, arg0 = _first_argmax(score, 1)
+    best1, arg1 = _first_argmax(score, 0)
+    ref = dict(zls0=z0, zls1=z1, lse0=l0, lse1=l1, score=score, best0=best0, best1=best1, arg0=arg0, arg1=arg1)
+    refs = (z0, z1, l0, l1, best0, best1, score)
+    yard = dict(zls=0.0, lse=0.0, best=0.0, dense=0.0)
+    for s in range(HEAD_PERMS):
+        gp = torch.Generator().manual_seed(1000 * seed + s)
+        pr_, pc_, pw_ = (torch.randperm(k_, generator=gp) if s else torch.arange(k_) for k_ in (m, n, width))
+        y0, y1, yl0, yl1, ys = _assign_eval(sim[pr_][:, pc_], d0[pr_][:, pw_], d1[pc_][:, pw_], w[pw_], b, torch.float32)
+        ir, ic = torch.argsort(pr_), torch.argsort(pc_)
+        ys = ys[ir][:, ic]
+        e = _assign_errors((y0[ir], y1[ic], yl0[ir], yl1[ic], ys.amax(dim=1), ys.amax(dim=0), ys), refs)
+        yard = {k_: max(yard[k_], e[k_]) for k_ in yard}
+    # margins of the integer outputs, on the reference (duplicates of a tie taken out: their gap is 0 by construction)
+    need = HEAD_MARGIN * HEAD_FACTOR * max(yard["best"], yard["dense"])
+    red = score[keep_r][:, keep_c]
+    for dim in (1, 0):
+        if red.shape[dim] >= 2:
+            top = red.topk(2, dim=dim).values
+            gap = (top.select(dim, 0) - top.select(dim, 1)).min().item()
+            if gap < need:
+                return None
+    if family == "planted":
+        mutual = arg1[arg0] == rows
+        ms = torch.where(mutual, best0.exp(), torch.zeros_like(best0))
+        if bool(((ms - ASSIGN_THR).abs()[mutual] < need).any()):
+            return None
+        on = torch.zeros(m, dtype=torch.bool)
+        on[planted[0]] = True
+        classes = (int((mutual & (ms > ASSIGN_THR) & on).sum()), int((~mutual).sum()), int((mutual & (ms <= ASSIGN_THR)).sum()))
+        if min(m, n) >= 60:
+            assert min(classes) > 0, ("planted: matches above the threshold on planted points, non-mutual rows and mutual rows below it", classes)
+    if family == "ramp":
+        for k_ in range(min(64, m)):   # the rows one thread of lg_col_stats4_kernel walks: its running maximum moves at every step
+            chain = sim[k_::64]
+            if chain.shape[0] > 1:
+                assert bool((chain[1:] > chain[:-1].cummax(dim=0).values).all()), "ramp: a column's running maximum does not move"
+    if tie_c:
+        hit = (arg0 == tie_c[0]) & (score[:, tie_c[1]] == best0)
+        assert bool(hit.any()), "ties: no row has its maximum in the tied columns"
+    if tie_r:
+        hit = (arg1 == tie_r[0]) & (score[tie_r[1]] == best1)
+        assert bool(hit.any()), "ties: no column has its maximum in the tied rows"
+    return AssignPair(sim, d0, d1, ref, yard, seed)
+
+
+@functools.lru_cache(maxsize=None)
+def assign_pair(width, m, n, family, ties, wrow, seed0):
+    """The first seed from seed0 on whose fp64 reference has the margins (see the section head)."""
+    for seed in range(seed0, seed0 + 300):
+        r = _assign_try(width, m, n, family, ties, wrow, seed)
+        if r is not None:
+            return r
+    raise AssertionError(f"no seed with the margins for {(width, m, n, family, ties)}")
+
+
+class HeadResult(NamedTuple):
+    figures: dict          # name -> (figure, yardstick) of the floating-point outputs
+    exact: dict            # name -> bool: the integer output equals the reference in every entry
+    untouched: bool        # every entry outside what the op must write, guard bands included, still holds the fill
+    repeatable: bool       # every run wrote the same bits
+    out: dict              # name -> the first run's tensor (CPU), for what a test looks at beyond this
+
+
+def assign_case(lib, width, nmax, nsel, counts, family, tag, done=None, ties=None, seed=1, device="cpu", runs=2, items=None, pad=float("nan")):
+    """dim_op_lg_assign_f32 on len(counts) pairs of (rows, columns) live points.  done: per pair (default: all == tag, or 1 .. for tag 0).  A pair runs
+    when done == tag (tag > 0: weight row tag - 1) or, tag == 0, when done > 0 (row done - 1 of the tables); the others must keep the fill.
+    items: (seed per pair), so that the same pair can sit in calls of different sizes.  pad: what the dead entries of sim hold (NaN; fmaxf and a compare
+    drop a NaN by themselves, so a second form with a huge finite value shows a missing mask in the statistics)."""
+    _bind_head(lib)
+    P = len(counts)
+    done = list(done) if done is not None else [tag if tag else 1 + i % HEAD_LAYERS for i in range(P)]
+    _, _, W, B = head_weights(width)
+    sim = torch.full((P, nmax, nmax), pad)
+    desc = torch.full((2 * P, nmax, width), float("nan"))
+    runs_pair = [(d == tag) if tag else d > 0 for d in done]
+    pairs = []
+    for i, (m, n) in enumerate(counts):
+        wrow = (tag if tag else max(done[i], 1)) - 1
+        pr = assign_pair(width, m, n, family, ties, wrow, (items[i] if items else 100 * seed + i)) if m and n else None
+        pairs.append(pr)
+        if pr is not None:
+            sim[i, :m, :n], desc[2 * i, :m], desc[2 * i + 1, :n] = pr.sim, pr.d0, pr.d1
+        else:   # an empty side: descriptors only
+            gi = torch.Generator().manual_seed(7 + i)
+            desc[2 * i, :m], desc[2 * i + 1, :n] = torch.randn(m, width, generator=gi), torch.randn(n, width, generator=gi)
+    n_cur = torch.tensor([c for mn in counts for c in mn], dtype=torch.int32)
+    simd, descd, nd, dd = sim.to(device), desc.to(device), n_cur.to(device), torch.tensor(done, dtype=torch.int32).to(device)
+    wd, bd = (W[tag - 1].contiguous().to(device), B[tag - 1:tag].contiguous().to(device)) if tag else (W.contiguous().to(device), B.to(device))
+    raws = []
+    for _ in range(runs):
+        o = {k: _filled(2 * P * nmax, torch.float32, device) for k in ("zls", "rmax", "rlse", "best")}
+        o["arg"] = _filled(2 * P * nmax, torch.int32, device)
+        dense = _filled(P * (nmax + 1) ** 2, torch.float32, device)
+        hs = _head_state(width, P, nmax, nsel, desc=descd, sim=simd, n_cur=nd, done=dd, **o)
+        rc = lib.dim_op_lg_assign_f32(ctypes.byref(hs), tag, p(wd), p(bd), p(dense), None)
+        assert rc == 0, lib.dim_last_error()
+        _sync(device)
+        raws.append(tuple(o[k].cpu() for k in ("zls", "rmax", "rlse", "best", "arg")) + (dense.cpu(),))
+    zls, rmax, rlse, best, arg, dense = raws[0]
+    N = 2 * P * nmax
+    live = torch.zeros(2 * P, nmax, dtype=torch.bool)
+    dlive = torch.zeros(P, nmax + 1, nmax + 1, dtype=torch.bool)
+    figs = {k: [0.0, 0.0] for k in ("zls", "lse", "best", "dense")}
+    arg_ok = True
+    v = lambda t: t[:N].view(2 * P, nmax)
+    for i, (m, n) in enumerate(counts):
+        if not runs_pair[i]:
+            continue
+        live[2 * i, :m], live[2 * i + 1, :n] = True, True
+        pr = pairs[i]
+        if pr is None:   # zls only: no row and no column statistics exist (the kernels write what they compute: -inf / log 0 / the sentinel index)
+            wrow = (tag if tag else done[i]) - 1
+            for s_, k_ in ((0, m), (1, n)):
+                if k_:
+                    zr = F.logsigmoid(desc[2 * i + s_, :k_].double() @ W[wrow].double() + B[wrow].double())
+                    figs["zls"][0] = max(figs["zls"][0], (v(zls)[2 * i + s_, :k_].double() - zr).abs().max().item())
+            continue
+        dlive[i, :m, :n] = True
+        out = (v(zls)[2 * i, :m], v(zls)[2 * i + 1, :n], v(rmax)[2 * i, :m].double() + v(rlse)[2 * i, :m].double(),
+               v(rmax)[2 * i + 1, :n].double() + v(rlse)[2 * i + 1, :n].double(), v(best)[2 * i, :m], v(best)[2 * i + 1, :n],
+               dense[:P * (nmax + 1) ** 2].view(P, nmax + 1, nmax + 1)[i, :m, :n])
+        r = pr.ref
+        e = _assign_errors(out, (r["zls0"], r["zls1"], r["lse0"], r["lse1"], r["best0"], r["best1"], r["score"]))
+        for k in figs:
+            figs[k] = [max(figs[k][0], e[k]), max(figs[k][1], pr.yard[k])]
+        arg_ok = arg_ok and torch.equal(v(arg)[2 * i, :m].long(), r["arg0"]) and torch.equal(v(arg)[2 * i + 1, :n].long(), r["arg1"])
+    untouched = True
+    for raw in raws:
+        for t in raw[:5]:   # (the live rows of an item whose other side is empty are written too, with -inf / the sentinel index: not compared)
+            untouched = untouched and bool(_is_fill(t[N:]).all()) and bool(_is_fill(t[:N][~live.view(-1)]).all())
+        D = P * (nmax + 1) ** 2
+        untouched = untouched and bool(_is_fill(raw[5][D:]).all()) and bool(_is_fill(raw[5][:D][~dlive.view(-1)]).all())
+    return HeadResult({k: tuple(x) for k, x in figs.items()}, {"arg": arg_ok}, untouched, _same_bits(raws),
+                      dict(zls=v(zls), rmax=v(rmax), rlse=v(rlse), best=v(best), arg=v(arg), dense=dense[:P * (nmax + 1) ** 2].view(P, nmax + 1, nmax + 1), live=live))
+
+
+def check_head(r, what=""):
+    """Same bits from every run, nothing written outside the live entries, every integer output exact, every figure (printed first) within HEAD_FACTOR x
+    its fp32 yardstick."""
+    print(f"lg head {what}: " + " ".join(f"{k} {f:.4g}/{y:.4g}" for k, (f, y) in r.figures.items()) + f" exact {r.exact} repeatable {r.repeatable} untouched {r.untouched}")
+    assert r.repeatable, "two runs on the same inputs differ"
+    assert r.untouched, "an entry outside the live ones (a dead row, a stopped pair, the guard band) was written"
+    assert all(r.exact.values()), r.exact
+    for k, (f, y) in r.figures.items():
+        assert f <= HEAD_FACTOR * y, (k, f, y)
+
+
+ASSIGN_COUNTS = ((130, 129), (1, 131), (131, 1), (64, 65))
+ASSIGN_BIG = ((37, 2049), (2049, 37))
+# (name, nmax = nsel, counts): the 16-byte kernels with rows in 8 registers per lane, in 16, and the generic kernels (nmax no multiple of 4)
+ASSIGN_PATHS = {"fast8": (132, ASSIGN_COUNTS), "fast16": (2052, ASSIGN_BIG), "generic": (134, ASSIGN_COUNTS)}
+
+
+def assign_path_case(lib, width, path, family, ties=None, device="cpu", runs=2, pad=float("nan")):
+    nmax, counts = ASSIGN_PATHS[path]
+    if ties:   # the tied rows and columns need (130, 129) / (2049, 37) + (37, 2049)
+        counts = counts[:1] if path != "fast16" else counts
+    return assign_case(lib, width, nmax, nmax, counts, family, 3, ties=ties, seed=11 if path == "fast16" else 1, device=device, runs=runs, pad=pad)
+
+
+def assign_stopped_case(lib, width, tag, device="cpu", runs=2):
+    """tag 5: pairs 1 (stopped at layer 2) and 2 (left without keypoints) are not selected.  tag 0: pairs 0, 1, 3 stopped at layers 2, 5, 9 run with
+    their own weight rows, pair 2 (still running) is not selected."""
+    done = (5, 2, -3, 5) if tag else (2, 5, 0, 9)
+    r = assign_case(lib, width, 132, 132, ASSIGN_COUNTS, "flat", tag, done=done, seed=2, device=device, runs=runs)
+    skipped = [i for i, d in enumerate(done) if not ((d == tag) if tag else d > 0)]
+    for i in skipped:   # (untouched covers it; spelled out because it is what the case is for)
+        for k in ("zls", "rmax", "rlse", "best", "arg"):
+            assert bool(_is_fill(r.out[k][2 * i:2 * i + 2].reshape(-1)).all()), (k, i)
+        assert bool(_is_fill(r.out["dense"][i].reshape(-1)).all())
+    return r
+
+
+def head_ragged(n_items, nmax, seed):
+    """Ragged counts in 0 .. nmax per item; the first pairs pinned to (nmax, 1), (0, nmax), (1, nmax - 1)."""
+    ns = torch.randint(2, nmax + 1, (n_items,), generator=torch.Generator().manual_seed(seed)).tolist()
+    ns[:6] = [nmax, 1, 0, nmax, 1, nmax - 1]
+    return tuple((ns[2 * i], ns[2 * i + 1]) for i in range(n_items // 2))
+
+
+def assign_occupancy_case(lib, width, device="cuda", runs=2):
+    """16 pairs x nmax 260 with ragged counts (hardware: many workgroups resident at once), planted."""
+    return assign_case(lib, width, 260, 260, head_ragged(32, 260, 5), "planted", 4, seed=3, device=device, runs=runs)
+
+
+def assign_alone_and_among(lib, width, device="cuda"):
+    """-> (a pair alone, the same pair as pair 9 of 16): its outputs must be the same bits."""
+    counts = head_ragged(32, 260, 5)
+    items = tuple(300 + i for i in range(16))
+    among = assign_case(lib, width, 260, 260, counts, "flat", 4, device=device, runs=1, items=items)
+    alone = assign_case(lib, width, 260, 260, counts[9:10], "flat", 4, device=device, runs=1, items=items[9:10])
+    return alone, among
+
+
+# ---- finalize ----
+FINAL_THR, FINAL_LAYERS = 0.1, 9
+ULP32 = 2.0 ** -23
+# exp(best): the device's expf and the host's are specified to 1 ulp and the fp64 reference rounds once more, so a match score is within 2 ulp of exp in
+# fp64 of the same fp32 `best`: figure = max relative error, "yardstick" 1 ulp, bound HEAD_FACTOR x that.
+
+
+@functools.lru_cache(maxsize=None)
+def _finalize_pair(m, n, mo, no, identity, bad, seed0):
+    """Hand-built state of one pair: ind (a sorted subset of the original indices unless identity), arg with ~60 % of the smaller side mutual and the
+    rest random (mostly not mutual), best0 = log of a score in 0.02 .. 0.98 — so there are valid matches, mutual rows below the threshold and
+    non-mutual rows; prune counters 1 .. 8.  bad: row 7 and column 11 carry ARG_NONE (row 9 points at column 11, column 3 at row 7, the last column at row 7 and
+    the last row at column 11)."""
+    for seed in range(seed0, seed0 + 100):
+        g = torch.Generator().manual_seed(seed)
+        ind0 = torch.arange(m) if identity else torch.randperm(mo, generator=g)[:m].sort().values
+        ind1 = torch.arange(n) if identity else torch.randperm(no, generator=g)[:n].sort().values
+        k = max(1, round(0.6 * min(m, n)))
+        pr, pc = torch.randperm(m, generator=g)[:k], torch.randperm(n, generator=g)[:k]
+        arg0, arg1 = torch.randint(0, n, (m,), generator=g), torch.randint(0, m, (n,), generator=g)
+        arg0[pr], arg1[pc] = pc, pr
+        if bad:
+            arg0[7], arg1[11], arg0[9], arg1[3] = ARG_NONE, ARG_NONE, 11, 7
+            arg1[n - 1], arg0[m - 1] = 7, 11   # (what an index clamped into range would find: still no match)
+        best0 = (0.02 + 0.96 * torch.rand(m, generator=g)).log()
+        best1 = (0.02 + 0.96 * torch.rand(n, generator=g)).log()
+        prune0, prune1 = torch.randint(1, 9, (mo,), generator=g), torch.randint(1, 9, (no,), generator=g)
+        if bool(((best0.double().exp() - FINAL_THR).abs() < HEAD_MARGIN * HEAD_FACTOR * ULP32).any()):
+            continue
+        return ind0, ind1, arg0, arg1, best0, best1, prune0, prune1
+    raise AssertionError("no seed with the margin")
+
+
+def _finalize_reference(m, n, st, nmax, thr):
+    """LightGlue's filter_matches (LGN:281-297) and the scatter through ind (LGN:543-566) in fp64; an arg outside the other side's range is "no match"."""
+    ind0, ind1, arg0, arg1, best0 = st[0], st[1], st[2], st[3], st[4]
+    in0, in1 = (arg0 >= 0) & (arg0 < n), (arg1 >= 0) & (arg1 < m)
+    a0, a1 = arg0.clamp(0, max(n - 1, 0)), arg1.clamp(0, max(m - 1, 0))
+    mutual0 = in0 & (arg1[a0] == torch.arange(m))
+    mutual1 = in1 & (arg0[a1] == torch.arange(n))
+    ms0 = torch.where(mutual0, best0.double().exp(), torch.zeros(m, dtype=torch.float64))
+    ms1 = torch.where(mutual1, ms0[a1], torch.zeros(n, dtype=torch.float64))
+    valid0 = mutual0 & (ms0 > thr)
+    valid1 = mutual1 & valid0[a1]
+    mfull, msfull = torch.full((2, nmax), -1, dtype=torch.int64), torch.zeros(2, nmax, dtype=torch.float64)
+    mfull[0, ind0], msfull[0, ind0] = torch.where(valid0, ind1[a0], -1), ms0
+    mfull[1, ind1], msfull[1, ind1] = torch.where(valid1, ind0[a1], -1), ms1
+    rows = torch.nonzero(valid0).flatten()
+    return mfull, msfull, torch.stack([ind0[rows], ind1[a0[rows]]], dim=1), ms0[rows], (int(valid0.sum()), int((~mutual0).sum()), int((mutual0 & ~valid0).sum()))
+
+
+# (m, n, m_orig, n_orig, done): rows-per-thread split above 1024 rows, its transpose, three pruned 130 x 130 pairs: stopped, still running, left without keypoints
+FINAL_PAIRS = ((1030, 37, 1032, 40, 5), (37, 1030, 37, 1032, 9), (130, 130, 150, 141, 3), (130, 130, 131, 150, 0), (130, 130, 140, 140, -4))
+
+
+def finalize_case(lib, out_cap, prune_enabled, bad=False, identity=False, device="cpu", width=256):
+    """dim_op_lg_finalize on FINAL_PAIRS (state given directly), twice on 0xff-filled outputs and once more on 0x5a-filled ones (a -1 that was never
+    written is then visible).  bad: pair 2 carries ARG_NONE in one row and one column."""
+    _bind_head(lib)
+    P, nmax = len(FINAL_PAIRS), 1032
+    best, arg = torch.full((2 * P, nmax), float("nan")), torch.full((2 * P, nmax), ARG_NONE, dtype=torch.int32)   # dead rows: NaN / an index that must not be followed
+    ind, prune = torch.full((2 * P, nmax), ARG_NONE, dtype=torch.int32), torch.full((2 * P, nmax), -77, dtype=torch.int32)
+    n_cur, n_orig, done = [], [], []
+    exp = []
+    for i, (m, n, mo, no, dn) in enumerate(FINAL_PAIRS):
+        st = _finalize_pair(m, n, mo, no, identity and i < 2, bad and i == 2, 50 + i)
+        ind[2 * i, :m], ind[2 * i + 1, :n], arg[2 * i, :m], arg[2 * i + 1, :n] = st[0].int(), st[1].int(), st[2].int(), st[3].int()
+        best[2 * i, :m], best[2 * i + 1, :n], prune[2 * i, :mo], prune[2 * i + 1, :no] = st[4], st[5], st[6].int(), st[7].int()
+        n_cur += [m, n]; n_orig += [mo, no]; done.append(dn)
+        mfull, msfull, mt, msc, classes = _finalize_reference(m, n, st, nmax, FINAL_THR)
+        if dn > 0 and i >= 2:
+            assert min(classes) > 0 and classes[0] > 60, classes
+        if dn <= 0:   # "no keypoints" exit / still running: no matches
+            mfull, msfull, mt, msc = torch.full_like(mfull, -1), torch.zeros_like(msfull), mt[:0], msc[:0]
+        po = torch.zeros(2, nmax, dtype=torch.int64)
+        po[0, :mo], po[1, :no] = (st[6] if prune_enabled else FINAL_LAYERS), (st[7] if prune_enabled else FINAL_LAYERS)
+        exp.append((mfull, msfull, mt, msc, po))
+    dev = lambda t, dt=torch.int32: torch.tensor(t, dtype=dt).to(device)
+    ins = dict(best=best.to(device), arg=arg.to(device), ind=ind.to(device), prune=prune.to(device), n_cur=dev(n_cur), n_orig=dev(n_orig), done=dev(done))
+    raws, ok, unt, fig = [], {k: True for k in ("matches", "n_matches", "mfull", "stop", "prune_out")}, True, 0.0
+    for fill in (0xff, 0xff, 0x5a):
+        o = dict(matches=_filled(P * out_cap * 2, torch.int64, device, fill), mscores=_filled(P * out_cap, torch.float32, device, fill),
+                 n_matches=_filled(P, torch.int32, device, fill), mfull=_filled(2 * P * nmax, torch.int32, device, fill),
+                 msfull=_filled(2 * P * nmax, torch.float32, device, fill), stop=_filled(P, torch.int32, device, fill),
+                 prune_out=_filled(2 * P * nmax, torch.int32, device, fill))
+        hs = _head_state(width, P, nmax, 1030, **ins)
+        rc = lib.dim_op_lg_finalize(ctypes.byref(hs), FINAL_LAYERS, prune_enabled, FINAL_THR, out_cap, *(p(o[k]) for k in
+                                    ("matches", "mscores", "n_matches", "mfull", "msfull", "stop", "prune_out")), None)
+        assert rc == 0, lib.dim_last_error()
+        _sync(device)
+        c = {k: t.cpu() for k, t in o.items()}
+        if fill == 0xff:
+            raws.append(tuple(c.values()))
+        for k, numel in (("matches", P * out_cap * 2), ("mscores", P * out_cap), ("n_matches", P), ("mfull", 2 * P * nmax), ("msfull", 2 * P * nmax), ("stop", P), ("prune_out", 2 * P * nmax)):
+            unt = unt and bool(_is_fill(c[k][numel:], fill).all())
+        mt_o, ms_o = c["matches"][:P * out_cap * 2].view(P, out_cap, 2), c["mscores"][:P * out_cap].view(P, out_cap)
+        mf_o, msf_o, po_o = (c[k][:2 * P * nmax].view(P, 2, nmax) for k in ("mfull", "msfull", "prune_out"))
+        for i, (mfull, msfull, mt, msc, po) in enumerate(exp):
+            k = min(mt.shape[0], out_cap)
+            ok["n_matches"] = ok["n_matches"] and int(c["n_matches"][i]) == k
+            ok["stop"] = ok["stop"] and int(c["stop"][i]) == abs(FINAL_PAIRS[i][4])
+            ok["matches"] = ok["matches"] and torch.equal(mt_o[i, :k], mt[:k])
+            ok["mfull"] = ok["mfull"] and torch.equal(mf_o[i].long(), mfull)
+            ok["prune_out"] = ok["prune_out"] and torch.equal(po_o[i].long(), po)
+            unt = unt and bool(_is_fill(mt_o[i, k:].reshape(-1), fill).all()) and bool(_is_fill(ms_o[i, k:].reshape(-1), fill).all())
+            ok["mfull"] = ok["mfull"] and torch.equal(msf_o[i] == 0, msfull == 0)   # exact zeros where there is no mutual match
+            for got, ref in ((ms_o[i, :k].double(), msc[:k]), (msf_o[i].double(), msfull)):
+                nz = ref > 0
+                if bool(nz.any()):
+                    fig = max(fig, ((got[nz] - ref[nz]).abs() / ref[nz]).max().item())
+    return HeadResult({"score": (fig, ULP32)}, ok, unt, _same_bits(raws), dict(mfull=mf_o, msfull=msf_o, n_matches=c["n_matches"][:P], matches=mt_o, exp=exp))
+
+
+# ---- prune ----
+PRUNE_MIN, PRUNE_WIDTH_CONF, PRUNE_THR = 40, 0.99, 0.85
+# (rows side 0, rows side 1, done, kind of each side): the scan with two rows per thread (1030), n == pruning_min and + 1, a side that loses nothing,
+# a side that loses everything, a stopped pair
+PRUNE_PAIRS = ((130, 1030, 0, "nn"), (PRUNE_MIN, PRUNE_MIN + 1, 0, "nn"), (130, 130, 0, "kn"), (130, 64, 0, "an"), (100, 90, 3, "nn"), (1030, 130, 0, "nn"))
+
+
+def prune_ws_layout(width, n_items, nmax):
+    """Byte offsets of tdesc | tenc | tind in the workspace of dim_op_lg_prune (each piece rounded up to 256 bytes) and the total."""
+    up = lambda v: (v + 255) // 256 * 256
+    rows = n_items * nmax
+    tenc = up(rows * width * 4)
+    tind = tenc + up(rows * (64 if width == 256 else 96) * 4)
+    return 0, tenc, tind, tind + up(rows * 4)
+
+
+def _prune_scores(n_cur, done, kinds, nmax, seed, exact_rows):
+    """conf, mtch [items][nmax] (NaN at or past n): mtch = u^6 (46 % at or below the keep threshold 0.01), conf = u.  kind k: mtch in 0.5 .. 1 (nothing goes);
+    a: mtch below 0.005 and conf above 0.9 (everything goes).  exact_rows: item 0 holds mtch == the threshold itself in row 2 (not kept: the compare is >)
+    and conf == its threshold in row 4 with a small mtch (kept with the token: the compare is <=)."""
+    g = torch.Generator().manual_seed(seed)
+    I = len(n_cur)
+    conf, mtch = torch.full((I, nmax), float("nan")), torch.full((I, nmax), float("nan"))
+    for it in range(I):
+        n, kind = int(n_cur[it]), kinds[it]
+        u, c = torch.rand(n, generator=g), torch.rand(n, generator=g)
+        mtch[it, :n] = u ** 6 if kind == "n" else (0.5 + 0.5 * u if kind == "k" else 0.005 * u)
+        conf[it, :n] = c if kind != "a" else 0.9 + 0.1 * c
+    if exact_rows and n_cur[0] > 4:
+        mtch[0, 2], conf[0, 2] = torch.tensor(1.0 - PRUNE_WIDTH_CONF, dtype=torch.float32), 0.95
+        mtch[0, 4], conf[0, 4] = 0.001, torch.tensor(PRUNE_THR, dtype=torch.float32)
+    return conf, mtch
+
+
+def prune_reference(s, conf, mtch, layer, use_token, nmax):
+    """One pruning pass (LGN:501-516, 586-591) on the state s (dict of CPU tensors, changed in place): a boolean-mask ordered compaction.
+    -> (dest, n_new, per item: did its rows move) with -2 / -2 where nothing is written."""
+    keep_thr, thr = torch.tensor(1.0 - PRUNE_WIDTH_CONF, dtype=torch.float32), torch.tensor(PRUNE_THR, dtype=torch.float32)
+    I = s["n_cur"].numel()
+    dest, n_new, moved = torch.full((I, nmax), -2, dtype=torch.int64), torch.full((I,), -2, dtype=torch.int64), [False] * I
+    for it in range(I):
+        if int(s["done"][it // 2]) != 0:
+            continue
+        n = int(s["n_cur"][it])
+        n_new[it] = n
+        if n <= PRUNE_MIN:
+            continue
+        keep = mtch[it, :n] > keep_thr
+        if use_token:
+            keep = keep | (conf[it, :n] <= thr)
+        dest[it, :n] = torch.where(keep, torch.cumsum(keep, 0) - 1, -1)
+        k = int(keep.sum())
+        n_new[it] = k
+        s["prune"][it, s["ind"][it, :n][keep].long()] += 1
+        if k < n:
+            moved[it] = True
+            for name in ("desc", "enc", "ind"):
+                s[name][it, :k] = s[name][it, :n][keep]
+    for pr in range(I // 2):
+        if int(s["done"][pr]) == 0:
+            s["n_cur"][2 * pr:2 * pr + 2] = n_new[2 * pr:2 * pr + 2].int()
+            if int(n_new[2 * pr]) == 0 or int(n_new[2 * pr + 1]) == 0:
+                s["done"][pr] = -(layer + 2)
+    return dest, n_new, moved
+
+
+def prune_initial_state(width, pairs, nmax, seed):
+    g = torch.Generator().manual_seed(seed)
+    I, ew = 2 * len(pairs), 64 if width == 256 else 96
+    n_cur = torch.tensor([c for pr in pairs for c in pr[:2]], dtype=torch.int32)
+    desc, enc = torch.full((I, nmax, width), float("nan")), torch.full((I, nmax, ew), float("nan"))
+    for it in range(I):
+        desc[it, :n_cur[it]], enc[it, :n_cur[it]] = torch.randn(int(n_cur[it]), width, generator=g), torch.randn(int(n_cur[it]), ew, generator=g)
+    return dict(desc=desc, enc=enc, ind=torch.arange(nmax, dtype=torch.int32).repeat(I, 1), prune=torch.ones(I, nmax, dtype=torch.int32), n_cur=n_cur,
+                done=torch.tensor([pr[2] for pr in pairs], dtype=torch.int32))
+
+
+def _bits_equal(a, b):
+    return torch.equal(a.contiguous().view(-1).view(torch.uint8), b.contiguous().view(-1).view(torch.uint8))
+
+
+def prune_round(lib, width, state, kinds, layer, use_token, nmax, nsel, seed, exact_rows=False, device="cpu"):
+    """dim_op_lg_prune on `state` (not modified) -> (HeadResult, the reference state after the pass).  Twice on 0xff-filled outputs and workspace and once
+    on 0x5a-filled ones (dest holds -1 for a dropped point)."""
+    _bind_head(lib)
+    I = state["n_cur"].numel()
+    conf, mtch = _prune_scores(state["n_cur"], state["done"], kinds, nmax, seed, exact_rows)
+    after = {k: t.clone() for k, t in state.items()}
+    dest, n_new, moved = prune_reference(after, conf, mtch, layer, use_token, nmax)
+    nbytes = int(lib.dim_op_lg_prune_workspace_bytes(width, I, nmax))
+    o_desc, o_enc, o_ind, total = prune_ws_layout(width, I, nmax)
+    assert nbytes == total
+    names = ("desc", "enc", "ind", "prune", "n_cur", "done")
+    ok, unt, raws = {k: True for k in names + ("dest", "n_new", "scratch")}, True, []
+    confd, mtchd = conf.to(device), mtch.to(device)
+    ew = 64 if width == 256 else 96
+    for fill in (0xff, 0xff, 0x5a):
+        io = {k: _guarded(state[k], device, fill) for k in names}
+        o = dict(dest=_filled(I * nmax, torch.int32, device, fill), n_new=_filled(I, torch.int32, device, fill))
+        ws = torch.full((nbytes + 16,), fill, dtype=torch.uint8, device=device)
+        hs = _head_state(width, I // 2, nmax, nsel, conf=confd, mtch=mtchd, **io, **o)
+        rc = lib.dim_op_lg_prune(ctypes.byref(hs), layer, PRUNE_WIDTH_CONF, PRUNE_THR, use_token, PRUNE_MIN, p(ws), None)
+        assert rc == 0, lib.dim_last_error()
+        _sync(device)
+        c = {k: t.cpu() for k, t in {**io, **o}.items()}
+        wsc = ws.cpu()
+        if fill == 0xff:
+            raws.append(tuple(c.values()))
+        for k in names:
+            numel = state[k].numel()
+            ok[k] = ok[k] and _bits_equal(c[k][:numel], after[k])
+            unt = unt and bool(_is_fill(c[k][numel:], fill).all())
+        d_o, n_o = c["dest"][:I * nmax].view(I, nmax), c["n_new"][:I]
+        written = dest != -2
+        ok["dest"] = ok["dest"] and torch.equal(d_o.long()[written], dest[written])
+        ok["n_new"] = ok["n_new"] and torch.equal(n_o.long()[n_new != -2], n_new[n_new != -2])
+        unt = unt and bool(_is_fill(d_o[~written], fill).all()) and bool(_is_fill(n_o[n_new == -2], fill).all())
+        unt = unt and bool(_is_fill(c["dest"][I * nmax:], fill).all()) and bool(_is_fill(c["n_new"][I:], fill).all()) and bool((wsc[nbytes:] == fill).all())
+        for it in range(I):   # an item whose rows do not move (stopped, at or below pruning_min, nothing pruned) leaves its scratch alone
+            if not moved[it]:
+                for off, rowb in ((o_desc, width * 4), (o_enc, ew * 4), (o_ind, 4)):
+                    ok["scratch"] = ok["scratch"] and bool((wsc[off + it * nmax * rowb:off + (it + 1) * nmax * rowb] == fill).all())
+    return HeadResult({}, ok, unt, _same_bits(raws), dict(dest=dest, n_new=n_new, moved=moved, conf=conf, mtch=mtch)), after
+
+
+def prune_case(lib, width, use_token, pairs=PRUNE_PAIRS, nmax=1032, nsel=1030, device="cpu"):
+    """Two pruning rounds in sequence on `pairs` -> (result of round 1, of round 2, state after 1, after 2)."""
+    kinds = [k for pr in pairs for k in pr[3]]
+    s0 = prune_initial_state(width, pairs, nmax, 900 + width)
+    r1, s1 = prune_round(lib, width, s0, kinds, 2, use_token, nmax, nsel, 31, exact_rows=True, device=device)
+    r2, s2 = prune_round(lib, width, s1, ["n"] * len(kinds), 3, use_token, nmax, nsel, 32, device=device)
+    return r1, r2, s1, s2
+
+
+def prune_ragged_pairs(n_pairs, nmax, seed):
+    return tuple((m, n, 0, "nn") for m, n in head_ragged(2 * n_pairs, nmax, seed))
+
+
+# ---- confidence and decide ----
+CONF_NS, CONF_DONE, CONF_CNT0 = (1, 31, 32, 33, 130, 64, 50, 50), (0, 0, 0, 2), (3, 0, 7, 5)   # around the 32 rows of a workgroup; pair 3 stopped
+
+
+@functools.lru_cache(maxsize=None)
+def _confidence_inputs(width, ns, layer, seed0):
+    Wt, Bt, Wm, Bm = head_weights(width)
+    keep_thr = 1.0 - PRUNE_WIDTH_CONF
+    for seed in range(seed0, seed0 + 100):
+        g = torch.Generator().manual_seed(seed)
+        desc = [torch.randn(n, width, generator=g) for n in ns]
+        ref = [(torch.sigmoid(d.double() @ Wt[layer].double() + Bt[layer].double()), torch.sigmoid(d.double() @ Wm[layer].double() + Bm[layer].double())) for d in desc]
+        yard = [0.0, 0.0]
+        for s in range(HEAD_PERMS):
+            pw = torch.randperm(width, generator=torch.Generator().manual_seed(77 * seed + s)) if s else torch.arange(width)
+            for d, (rc_, rm_) in zip(desc, ref):
+                yard[0] = max(yard[0], (torch.sigmoid(d[:, pw] @ Wt[layer][pw] + Bt[layer]).double() - rc_).abs().max().item())
+                yard[1] = max(yard[1], (torch.sigmoid(d[:, pw] @ Wm[layer][pw] + Bm[layer]).double() - rm_).abs().max().item())
+        if all(bool(((rc_ - PRUNE_THR).abs() >= HEAD_MARGIN * HEAD_FACTOR * yard[0]).all()) and bool(((rm_ - keep_thr).abs() >= HEAD_MARGIN * HEAD_FACTOR * yard[1]).all())
+               for rc_, rm_ in ref):
+            return desc, ref, yard
+    raise AssertionError("no seed with the margins")
+
+
+def confidence_case(lib, width, use_token, ns=CONF_NS, done=CONF_DONE, nmax=132, nsel=130, device="cpu", runs=2, layer=4):
+    """dim_op_lg_confidence_f32: conf, mtch and the per-pair count of conf < PRUNE_THR on top of what cnt_lt held."""
+    _bind_head(lib)
+    I = len(ns)
+    descs, ref, yard = _confidence_inputs(width, tuple(ns), layer, 60)
+    Wt, Bt, Wm, Bm = head_weights(width)
+    desc = torch.full((I, nmax, width), float("nan"))
+    for it, d in enumerate(descs):
+        desc[it, :ns[it]] = d
+    cnt0 = torch.tensor([CONF_CNT0[i % 4] for i in range(I // 2)], dtype=torch.int32)
+    descd, nd, dd = desc.to(device), torch.tensor(ns, dtype=torch.int32).to(device), torch.tensor(done, dtype=torch.int32).to(device)
+    w = [t.contiguous().to(device) for t in (Wt[layer], Bt[layer:layer + 1], Wm[layer], Bm[layer:layer + 1])]
+    raws = []
+    for _ in range(runs):
+        o = dict(conf=_filled(I * nmax, torch.float32, device), mtch=_filled(I * nmax, torch.float32, device), cnt_lt=_guarded(cnt0, device))
+        hs = _head_state(width, I // 2, nmax, nsel, desc=descd, n_cur=nd, done=dd, **o)
+        rc = lib.dim_op_lg_confidence_f32(ctypes.byref(hs), p(w[0]), p(w[1]), p(w[2]), p(w[3]), PRUNE_THR, use_token, None)
+        assert rc == 0, lib.dim_last_error()
+        _sync(device)
+        raws.append(tuple(o[k].cpu() for k in ("conf", "mtch", "cnt_lt")))
+    conf, mtch, cnt = raws[0]
+    live = torch.zeros(I, nmax, dtype=torch.bool)
+    fc = fm = 0.0
+    cnt_ref = cnt0.clone().long()
+    for it in range(I):
+        if done[it // 2] != 0:
+            continue
+        live[it, :ns[it]] = True
+        co, mo = conf[:I * nmax].view(I, nmax)[it, :ns[it]].double(), mtch[:I * nmax].view(I, nmax)[it, :ns[it]].double()
+        fm = max(fm, (mo - ref[it][1]).abs().max().item())
+        if use_token:
+            fc = max(fc, (co - ref[it][0]).abs().max().item())
+            cnt_ref[it // 2] += int((ref[it][0] < PRUNE_THR).sum())
+        else:
+            fc = max(fc, co.abs().max().item())   # exact zeros
+    unt = all(bool(_is_fill(r[k][I * nmax:]).all()) and bool(_is_fill(r[k][:I * nmax][~live.view(-1)]).all()) for r in raws for k in (0, 1))
+    unt = unt and all(bool(_is_fill(r[2][I // 2:]).all()) for r in raws)
+    return HeadResult({"conf": (fc, yard[0] if use_token else 0.0), "mtch": (fm, yard[1])}, {"cnt_lt": torch.equal(cnt[:I // 2].long(), cnt_ref)}, unt,
+                      _same_bits(raws), dict(cnt_lt=cnt[:I // 2], cnt_ref=cnt_ref))
+
+
+DECIDE_DONE, DECIDE_NORIG = (0, 0, 0, 4, -2, 0, 0), ((100, 100), (100, 100), (130, 70), (50, 50), (0, 9), (1, 1), (2048, 2048))
+DECIDE_CNT, DECIDE_DEPTH_CONF = (3, 40, 11, 6, 0, 0, 200), 0.95   # confident ratios 0.985, 0.8, 0.945, -, -, 1.0, 0.951
+
+
+def decide_case(lib, early, last, layer=5, device="cpu", runs=2):
+    """dim_op_lg_decide: the early-stop decision (LGN:593-604) in the reference's own fp32 form, 1 - count / points > depth_confidence; the counters return
+    to 0 for every pair and a stopped pair keeps its layer."""
+    _bind_head(lib)
+    P = len(DECIDE_DONE)
+    done, cnt = torch.tensor(DECIDE_DONE, dtype=torch.int32), torch.tensor(DECIDE_CNT, dtype=torch.int32)
+    n_orig = torch.tensor([c for pr in DECIDE_NORIG for c in pr], dtype=torch.int32)
+    ratio64 = 1.0 - cnt.double() / n_orig.view(P, 2).sum(1).double()
+    assert bool(((ratio64 - DECIDE_DEPTH_CONF).abs() > 1e-4).all()) and bool((ratio64 > DECIDE_DEPTH_CONF).any()) and bool((ratio64 < DECIDE_DEPTH_CONF).any())
+    ratio = 1.0 - cnt.float() / n_orig.view(P, 2).sum(1).float()
+    stop = torch.full((P,), bool(last)) if last else (ratio > DECIDE_DEPTH_CONF) & bool(early)
+    ref = torch.where((done == 0) & stop, torch.full_like(done, layer + 1), done)
+    nd = n_orig.to(device)
+    raws = []
+    for _ in range(runs):
+        o = dict(done=_guarded(done, device), cnt_lt=_guarded(cnt, device))
+        hs = _head_state(256, P, 8, 8, n_orig=nd, **o)
+        rc = lib.dim_op_lg_decide(ctypes.byref(hs), layer, DECIDE_DEPTH_CONF, early, last, None)
+        assert rc == 0, lib.dim_last_error()
+        _sync(device)
+        raws.append(tuple(o[k].cpu() for k in ("done", "cnt_lt")))
+    unt = all(bool(_is_fill(r[k][P:]).all()) for r in raws for k in (0, 1))
+    return HeadResult({}, {"done": torch.equal(raws[0][0][:P], ref), "cnt_lt": bool((raws[0][1][:P] == 0).all())}, unt, _same_bits(raws), dict(done=raws[0][0][:P], ref=ref))

@@ -74,6 +74,14 @@ Case -> kernel (from launch_gemm / launch_gemm_x6 / launch_gemm_x6_nt / launch_c
     two_parts (E)     64 items, nsel 100            attn_x6_kernel<MODE> 512 wg + attn_combine_kernel<2>
     many_resident     256: 64 x 260 768 wg (1 part), 32 x 260 768 wg (2 parts), 20 x 260 960 wg (4 parts); 96: 64 x 400 512 wg (2 parts), 128 x 520 640 wg (1 part)
 
+  tests/test_lg_head_ops_gpu.py (dim_op_lg_confidence_f32 / dim_op_lg_decide / dim_op_lg_prune / dim_op_lg_assign_f32 / dim_op_lg_finalize; widths 256 and 96)
+    assign            nmax 132: lg_row_stats4<8> + lg_col_stats4 + lg_row_argmax4<8> + lg_col_argmax4; nmax 2052: the <16> forms; nmax 134: the generic four;
+                      flat / planted / ramp / ties / dead entries 1e30 / pairs the tag does not select
+    many_resident     16 pairs x 260 ragged (0, 1 and nmax among the counts): assign 2080 + 80 + 1040 + 80 wg, prune 32 + 2080 + 2080 wg; a pair alone and among 16
+    finalize          5 pairs, nmax 1032 (two rows per thread), out_cap 50 / 1032, done > 0 / 0 / < 0, prune on / off      lg_finalize_kernel 5 wg of 16 waves
+    prune             6 pairs, nmax 1032, two rounds            lg_prune_scan 12 wg, gather / copyback 258 x 12 wg (lgl_prune_* at width 96), commit 1 wg
+    confidence        n = 1, 31, 32, 33, 130, 64, 50, 50        lg_confidence_kernel / lgl_confidence_kernel 5 x 8 wg;   decide: lg_decide_kernel 1 wg
+
 launch_gemm_x6's gemm_x6_kernel<2,64,2,2> branch is not in the table: a small problem has cdiv(M,128) * cdiv(N,128) < 256 workgroups, so at most
 2 * 255 = 510 workgroups of 64 rows, which is never above the 512 that the branch before it accepts.
 """
