@@ -60,8 +60,12 @@ constexpr int w_slice(int npl) { return npl * 3 * 2 * 64 * 8; }              // 
 //     the largest of the four = max_pool(bn(relu(x))) for either sign of s.  With F1A conv1a's own s | t (b1a[64 + c], b1a[128 + c]) follow
 //     its ReLU for pixels inside the image; conv1b's zero padding stays zero.  A compile-time flag: every BN = false instantiation is the
 //     code it was.
-template <int CIN, int POOL, int PF, bool F1A, int MODE, bool PIN, bool POUT, int MR = 2, bool WDMA = false, bool BN = false>
-__global__ __launch_bounds__(256, ((PF == 2 || MR == 4) ? 2 : 3)) void conv3x3_x6_kernel(const float* __restrict__ in, const unsigned short* __restrict__ wx,
+// BLK (the VGG16 backbone of NetVLAD, K up to 9 x 512): blocked accumulation.  Every K chunk (16 channels x 9 taps x the cross terms) is summed from zero
+//     and then added to a second set of accumulators, so a result sees cin / 16 roundings at its full magnitude instead of one per MFMA (864 at
+//     cin 512 in fp16x3): measured on conv5_3 of the 48 x 64 parity case, the map's rms error against fp64 fell from 2.1 x to below that of an fp32
+//     torch convolution.  Twice the accumulator registers: 2 workgroups per CU.  A compile-time flag: every BLK = false instantiation is the code it was.
+template <int CIN, int POOL, int PF, bool F1A, int MODE, bool PIN, bool POUT, int MR = 2, bool WDMA = false, bool BN = false, bool BLK = false>
+__global__ __launch_bounds__(256, ((PF == 2 || MR == 4 || BLK) ? 2 : 3)) void conv3x3_x6_kernel(const float* __restrict__ in, const unsigned short* __restrict__ wx,
                                                             const float* __restrict__ bias, float* __restrict__ out, int H, int W,
                                                             int cout, int relu, int tiles_x, const float* __restrict__ w1a,
                                                             const float* __restrict__ b1a, const float* __restrict__ inv_ch, unsigned* sat,
@@ -101,6 +105,15 @@ __global__ __launch_bounds__(256, ((PF == 2 || MR == 4) ? 2 : 3)) void conv3x3_x
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+  f32x16 macc[BLK ? MR : 1][2];   // BLK: the sum of the finished chunks
+  if (BLK) {
+#pragma unroll
+    for (int i = 0; i < MR; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) macc[i][j][r] = 0.0f;
+  }
 
   constexpr int W_ITEMS = W_SLICE / 8;              // 16-B weight items per staging step
   constexpr int NWV = (W_ITEMS + 255) / 256;        // per thread (bf16x6: 4.5 -> 5; fp16x3: 3)
@@ -273,6 +286,20 @@ __global__ __launch_bounds__(256, ((PF == 2 || MR == 4) ? 2 : 3)) void conv3x3_x
             for (int n = 0; n < 2; ++n) acc[m][n] = S::mma(fa[m][S::ta(tm)], fb[n][S::tb(tm)], acc[m][n]);
       }
       __builtin_amdgcn_s_setprio(0);
+    }
+    if (BLK) {   // the chunk's sum joins the total (the last chunk leaves the total in acc for the epilogue)
+#pragma unroll
+      for (int i = 0; i < (BLK ? MR : 0); ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          macc[i][j] += acc[i][j];
+          if (c + 1 < NCHUNK) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+          } else {
+            acc[i][j] = macc[i][j];
+          }
+        }
     }
   }
 
@@ -662,6 +689,34 @@ int launch_planes_to_f32(const void* planes, int batch, int hw, int channels, fl
   const size_t n = (size_t)batch * hw * channels;
   if (n == 0) return 0;
   hipLaunchKernelGGL(planes_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const unsigned short*)planes, channels, hw, out, n);
+  DIM_LAUNCH_CHECK();
+  return 0;
+}
+
+// The VGG16 backbone of NetVLAD: the same kernel instantiated with blocked accumulation (BLK) at CIN 64 / 128 / 256 / 512 — fp32 NHWC in and out, 8-row
+// tiles, weight slices prefetched behind the MFMAs, no fused pool (the backbone pools with floor semantics in a pass of its own).  LDS does not depend on
+// CIN: only the K loop is longer.  fp16x3 (mode 2) or bf16x6 (mode 1) weights of prepare_conv_weights_split.
+int launch_conv3x3_x6_wide(const float* in, const SplitWeights& wt, const float* bias, float* out, int batch, int H, int W, int cin, int cout, int relu,
+                           hipStream_t s, unsigned* sat) {
+  DIM_REQUIRE(cout % 64 == 0, "conv3x3_x6 wide: cout=%d must be a multiple of 64", cout);
+  DIM_REQUIRE(cin == 64 || cin == 128 || cin == 256 || cin == 512, "conv3x3_x6 wide: cin=%d unsupported (64, 128, 256 or 512)", cin);
+  DIM_REQUIRE(wt.dev && (wt.mode == 1 || wt.mode == 2), "conv3x3_x6 wide: weights not prepared (mode %d)", wt.mode);
+  DIM_REQUIRE((size_t)H * W * cout * 4 < 0x7FFFFFF0ull, "conv3x3_x6 wide: one %d x %d x %d image exceeds the 2 GiB of a buffer descriptor", H, W, cout);
+  if (batch <= 0 || H <= 0 || W <= 0) return 0;
+  const int tiles_x = cdiv(W, TW), tiles_y = cdiv(H, tile_rows(2));
+  dim3 grid(tiles_x * tiles_y, cout / 64, batch);
+#define DIM_CONV6W(CI, MD) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_x6_kernel<CI, 0, 1, false, MD, false, false, 2, false, false, true>), grid, dim3(256), 0, s, in, wt.dev, bias, out, H, W, cout, relu, tiles_x, (const float*)nullptr, (const float*)nullptr, wt.inv_ch(), sat, (unsigned*)nullptr)
+#define DIM_CONV6W_CI(MD)                     \
+  {                                           \
+    if (cin == 64) DIM_CONV6W(64, MD);        \
+    else if (cin == 128) DIM_CONV6W(128, MD); \
+    else if (cin == 256) DIM_CONV6W(256, MD); \
+    else DIM_CONV6W(512, MD);                 \
+  }
+  if (wt.mode == 2) DIM_CONV6W_CI(2)
+  else DIM_CONV6W_CI(1)
+#undef DIM_CONV6W_CI
+#undef DIM_CONV6W
   DIM_LAUNCH_CHECK();
   return 0;
 }

@@ -98,6 +98,10 @@ void prepare_conv_weights_split(const float* w_oihw, int cin, int cout, int mode
 // SuperPoint takes: pooled fused conv1a, pre-split input AND output in the planes launcher, any launch_conv3x3_x6 shape.
 int launch_conv3x3_x6(const float* in, const SplitWeights& wt, const float* bias, float* out, int batch, int H, int W, int cin,
                       int cout, int pool, int relu, hipStream_t s, unsigned* sat = nullptr, int bn = 0);
+// the same convolution with blocked accumulation at cin 64 / 128 / 256 / 512 (VGG16 conv1_2 .. conv5_3: the NetVLAD backbone): fp32 in and out, no fused
+// pool, modes 1 and 2
+int launch_conv3x3_x6_wide(const float* in, const SplitWeights& wt, const float* bias, float* out, int batch, int H, int W, int cin, int cout, int relu,
+                           hipStream_t s, unsigned* sat = nullptr);
 // conv1a (image -> 64 channels, weights [9][64]) computed on the fly inside the following 64 -> cout conv
 int launch_conv3x3_x6_fused1a(const float* image, const float* w1a_tap_cout, const float* b1a, const SplitWeights& wt, const float* bias,
                               float* out, int batch, int H, int W, int cout, int pool, int relu, int planes_out, hipStream_t s,

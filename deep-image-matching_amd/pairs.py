@@ -56,8 +56,9 @@ def pairs_from_retrieval(query_names: Sequence[str], db_names: Sequence[str], qu
     (query by query, best first).  Only the (nq, k) index table leaves the device."""
     lib = lib if lib is not None else capi.load()
     dev = torch.device(device)
-    q = torch.as_tensor(np.asarray(query_desc), dtype=torch.float32)
-    d = torch.as_tensor(np.asarray(db_desc), dtype=torch.float32)
+    # device tensors (RetrievalPairSelector's descriptor table) are taken as they lie; anything else goes through numpy as before
+    as_f32 = lambda x: x.to(torch.float32) if torch.is_tensor(x) else torch.as_tensor(np.asarray(x), dtype=torch.float32)  # noqa: E731
+    q, d = as_f32(query_desc), as_f32(db_desc)
     nq, nd, D = q.shape[0], d.shape[0], q.shape[1]
     if nq == 0 or nd == 0:
         return []
@@ -158,3 +159,106 @@ class LowresPairSelector:
             return []
         counts = self.match_counts(self.extract(images), idx_pairs)
         return [(names[i], names[j]) for (i, j), c in zip(idx_pairs, counts) if c > self.min_matches]
+
+
+class RetrievalPairSelector:
+    """The ``retrieval`` strategy (pairs_generator.py:327-339 -> image_retrieval.py) with a resident NetVLAD: hloc's
+    ``extract_features.confs["netvlad"]`` preprocessing (RGB, ``resize_max`` 1024 with cv2 INTER_AREA, size rule ``int(round(x * scale))``,
+    thirdparty/hloc/extract_features.py:200-205; /255), the global descriptors (netvlad_hip.NetVLADHIP), hloc's ``pairs_from_retrieval`` on the
+    descriptor table as it lies in HBM, and image_retrieval.py:28-44's removal of duplicates.  ``images``: RGB float32 / uint8 arrays (0..255) in
+    list order.  Same-sized images go through the network in batches of up to ``max_batch``; only the (n, num_matched) index table leaves the
+    device."""
+
+    def __init__(self, netvlad_state, resize_max: int = 1024, max_batch: int = 8, conf: Optional[dict] = None, device="cuda", lib=None):
+        self.resize_max, self.max_batch = int(resize_max), int(max_batch)
+        self.device = torch.device(device)
+        self.lib = lib if lib is not None else capi.load()
+        self._state, self._conf = netvlad_state, dict(conf or {})
+        self._net = None
+        self._net_hw = (0, 0)
+
+    def _stream(self):
+        return capi.stream_ptr(self.device)
+
+    def _size(self, image: np.ndarray):
+        """(h, w) the network sees: thirdparty/hloc/extract_features.py:200-205."""
+        H, W = image.shape[:2]
+        if max(H, W) <= self.resize_max:
+            return H, W
+        scale = self.resize_max / max(W, H)
+        return int(round(H * scale)), int(round(W * scale))
+
+    def preprocess(self, image: np.ndarray, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[H,W,3] 0..255 -> [h,w,3] in 0..1 on the device (into ``out`` when given); down-sampled with the area kernel when max(size) > resize_max.
+        A non-finite pixel raises ValueError here, on the host: the network's clamp would read a NaN as 0 (include/dim_hip.h)."""
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError(f"RetrievalPairSelector: image of shape {tuple(image.shape)}, (H, W, 3) expected")
+        host = np.ascontiguousarray(image, dtype=np.float32)
+        if not np.isfinite(host).all():
+            raise ValueError("RetrievalPairSelector: image holds a non-finite value")
+        H, W = image.shape[:2]
+        h, w = self._size(image)
+        src = torch.as_tensor(host).to(self.device)
+        if out is None:
+            out = torch.empty(h, w, 3, dtype=torch.float32, device=self.device)
+        if (h, w) == (H, W):
+            torch.div(src, 255.0, out=out)
+            return out
+        planes = src.permute(2, 0, 1).contiguous()   # the area kernel takes single-channel planes
+        dst = torch.empty(3, h, w, dtype=torch.float32, device=self.device)
+        with capi.device_ctx(self.device):
+            for c in range(3):
+                capi.check(self.lib, self.lib.dim_op_resize_area_f32(capi.ptr(planes[c]), H, W, capi.ptr(dst[c]), h, w, 1, self._stream()))
+        out.copy_(dst.permute(1, 2, 0))
+        return out
+
+    def describe(self, images: Sequence[np.ndarray]) -> torch.Tensor:
+        """Descriptor table [n, dim] on the device, rows in list order.  Images are uploaded and preprocessed one batch at a time into one staging
+        buffer per size, so the device holds a batch of images, not the list."""
+        from .netvlad_hip import NetVLADHIP
+
+        sizes = [self._size(im) for im in images]
+        mh, mw = max(s[0] for s in sizes), max(s[1] for s in sizes)
+        if self._net is None or mh > self._net_hw[0] or mw > self._net_hw[1]:
+            self._net_hw = (max(mh, self._net_hw[0]), max(mw, self._net_hw[1]))
+            self._net = NetVLADHIP(self._state, self._conf, max_batch=self.max_batch, max_hw=self._net_hw, device=self.device, lib=self.lib)
+        by_size = {}
+        for i, s in enumerate(sizes):
+            by_size.setdefault(s, []).append(i)
+        order = [i for idx in by_size.values() for i in idx]   # processing order: size by size; descriptors land in consecutive rows of `work`
+        work = torch.empty(len(images), self._net.dim, dtype=torch.float32, device=self.device)
+
+        def run():   # every batch is enqueued back to back; the fp16x3 range guard is read once for the whole list
+            row = 0
+            for (h, w), idx in by_size.items():
+                stage = torch.empty(min(self.max_batch, len(idx)), h, w, 3, dtype=torch.float32, device=self.device)
+                for s0 in range(0, len(idx), self.max_batch):
+                    chunk = idx[s0:s0 + self.max_batch]
+                    for j, i in enumerate(chunk):
+                        self.preprocess(images[i], out=stage[j])
+                    self._net.extract_batch(stage[:len(chunk)], out=work[row:row + len(chunk)])
+                    row += len(chunk)
+
+        self._net.guarded(run, "retrieval")
+        if order == list(range(len(images))):
+            return work
+        inverse = torch.empty(len(order), dtype=torch.long)
+        inverse[torch.tensor(order)] = torch.arange(len(order))
+        return work[inverse.to(self.device)]
+
+    def select(self, names: Sequence, images: Sequence[np.ndarray], num_matched: int = 10, min_score: Optional[float] = 0.0) -> List[tuple]:
+        """(name, name) pairs: every image's ``num_matched`` most similar others, best first, query by query, similarities below ``min_score`` never
+        (0, as pairs_from_retrieval.main hands it to pairs_from_score_matrix, thirdparty/hloc/pairs_from_retrieval.py:112: an image may get fewer
+        pairs, or none); a pair that has already come out in either order is dropped (image_retrieval.py:34-42)."""
+        if len(names) < 2:
+            return []
+        names = list(names)
+        table = self.describe(images)
+        pairs = pairs_from_retrieval(names, names, table, table, num_matched, min_score=min_score, device=self.device, lib=self.lib)
+        seen, out = set(), []
+        for a, b in pairs:
+            key = tuple(sorted((a, b)))
+            if key not in seen:
+                seen.add(key)
+                out.append((a, b))
+        return out

@@ -660,3 +660,136 @@ def load_superglue_state_dict(path: str | None = None, seed: int = 0, allow_synt
     sd = {k: (v.float().contiguous() if v.is_floating_point() else v) for k, v in sd.items()}
     validate_superglue_state_dict(sd)
     return sd
+
+
+# ---- NetVLAD (thirdparty/hloc/extractors/netvlad.py, NV) -------------------------------------------------------------------------------
+# VGG16 features[:-2] (NV:66-68): (index in the Sequential = index in the checkpoint's net.layers, cout, cin); pools sit at 4, 9, 16, 23
+NETVLAD_CONVS = [(0, 64, 3), (2, 64, 64), (5, 128, 64), (7, 128, 128), (10, 256, 128), (12, 256, 256), (14, 256, 256),
+                 (17, 512, 256), (19, 512, 512), (21, 512, 512), (24, 512, 512), (26, 512, 512), (28, 512, 512)]
+NETVLAD_DIM = 512
+NETVLAD_MAT_LAYERS, NETVLAD_MAT_VLAD, NETVLAD_MAT_WHITEN = 35, 30, 33   # NV:79,93,107
+
+
+def netvlad_state_shapes(K: int = 64, whiten_out: Optional[int] = 4096) -> Dict[str, tuple]:
+    """The NetVLAD module's own state-dict keys (NV:68-73) plus ``preprocess.mean`` (NV:118); ``whiten_out`` None / 0: no whitening."""
+    t = {}
+    for i, co, ci in NETVLAD_CONVS:
+        t[f"backbone.{i}.weight"] = (co, ci, 3, 3)
+        t[f"backbone.{i}.bias"] = (co,)
+    t["netvlad.score_proj.weight"] = (K, NETVLAD_DIM, 1)
+    t["netvlad.centers"] = (NETVLAD_DIM, K)
+    if whiten_out:
+        t["whiten.weight"] = (whiten_out, NETVLAD_DIM * K)
+        t["whiten.bias"] = (whiten_out,)
+    t["preprocess.mean"] = (3,)
+    return t
+
+
+def validate_netvlad_state(sd: Dict[str, torch.Tensor]) -> tuple:
+    """(K, whiten_out or 0).  KeyError for a missing / unexpected tensor, ValueError for a wrong shape, a cluster count that is no multiple of 8 up
+    to 64 or a non-finite value — each naming the tensor — before anything native is called."""
+    if "netvlad.centers" not in sd:
+        raise KeyError("NetVLAD: state has no tensor 'netvlad.centers'")
+    c = sd["netvlad.centers"]
+    if c.dim() != 2 or c.shape[0] != NETVLAD_DIM or c.shape[1] % 8 != 0 or not 8 <= c.shape[1] <= 64:
+        raise ValueError(f"NetVLAD: tensor 'netvlad.centers' has shape {tuple(c.shape)}, expected ({NETVLAD_DIM}, K) with K a multiple of 8 up to 64")
+    K = int(c.shape[1])
+    wo = int(sd["whiten.bias"].shape[0]) if "whiten.bias" in sd and sd["whiten.bias"].dim() == 1 else 0
+    if ("whiten.weight" in sd) != ("whiten.bias" in sd):
+        raise KeyError("NetVLAD: 'whiten.weight' and 'whiten.bias' come together")
+    table = netvlad_state_shapes(K, wo)
+    for k, shape in table.items():
+        if k not in sd:
+            raise KeyError(f"NetVLAD: state has no tensor {k!r}")
+        if tuple(sd[k].shape) != tuple(shape):
+            raise ValueError(f"NetVLAD: tensor {k!r} has shape {tuple(sd[k].shape)}, expected {tuple(shape)}")
+        if not bool(torch.isfinite(sd[k]).all()):
+            raise ValueError(f"NetVLAD: tensor {k!r} holds a non-finite value")
+    for k in sd:
+        if k not in table:
+            raise KeyError(f"NetVLAD: unexpected tensor {k!r} in the state")
+    return K, wo
+
+
+def synthetic_netvlad_state(seed: int = 31, K: int = 64, whiten_out: Optional[int] = 4096) -> Dict[str, torch.Tensor]:
+    """Seeded synthetic NetVLAD weights under the module's keys.  He-normal convolutions with 0.1 N(0, 1) biases keep the second moment of the
+    activations from layer to layer (the normalised image has |x| <= 152), so they neither vanish nor leave the fp16x3 range; score weights
+    4 N(0, 1) (unit-norm inputs: soft assignments that are neither uniform nor one-hot), centres N(0, 1) / sqrt(512), whitening N(0, 1) / sqrt(512 K)
+    with a 0.01 N(0, 1) bias, mean = the ImageNet-like (123.68, 116.78, 103.94) the trained checkpoints carry to within a count."""
+    g = torch.Generator().manual_seed(seed)
+    sd: Dict[str, torch.Tensor] = {}
+    for k, shape in netvlad_state_shapes(K, whiten_out).items():
+        if k == "preprocess.mean":
+            sd[k] = torch.tensor([123.68, 116.78, 103.94])
+        elif k.startswith("backbone.") and len(shape) == 4:
+            sd[k] = torch.randn(shape, generator=g) * math.sqrt(2.0 / (shape[1] * 9))
+        elif k.startswith("backbone."):
+            sd[k] = 0.1 * torch.randn(shape, generator=g)
+        elif k == "netvlad.score_proj.weight":
+            sd[k] = 4.0 * torch.randn(shape, generator=g)
+        elif k == "netvlad.centers":
+            sd[k] = torch.randn(shape, generator=g) / math.sqrt(NETVLAD_DIM)
+        elif k == "whiten.weight":
+            sd[k] = torch.randn(shape, generator=g) / math.sqrt(shape[1])
+        else:
+            sd[k] = 0.01 * torch.randn(shape, generator=g)
+    return sd
+
+
+def netvlad_state_to_mat(sd: Dict[str, torch.Tensor]) -> dict:
+    """The dict ``scipy.io.savemat`` turns into the checkpoint layout NV:76-121 reads: ``net.layers`` a 35-element cell whose entries at the
+    backbone's convolution indices hold weights {HWIO, bias}, entry 30 {score (D, K), -centres (D, K)}, entry 33 {whitening (1, 1, IN, OUT), bias};
+    ``net.meta.normalization.averageImage`` a (2, 2, 3) array of the mean."""
+    import numpy as np
+
+    def cell(*items):
+        c = np.empty(len(items), dtype=object)
+        for i, it in enumerate(items):
+            c[i] = np.ascontiguousarray(it, dtype=np.float32)
+        return c
+
+    layers = np.empty(NETVLAD_MAT_LAYERS, dtype=object)
+    for i in range(NETVLAD_MAT_LAYERS):
+        layers[i] = {"type": "other"}
+    for i, _, _ in NETVLAD_CONVS:
+        layers[i] = {"type": "conv", "weights": cell(sd[f"backbone.{i}.weight"].permute(2, 3, 1, 0).numpy(), sd[f"backbone.{i}.bias"].numpy())}
+    layers[NETVLAD_MAT_VLAD] = {"type": "vlad", "weights": cell(sd["netvlad.score_proj.weight"][:, :, 0].t().numpy(), -sd["netvlad.centers"].numpy())}
+    if "whiten.weight" in sd:
+        layers[NETVLAD_MAT_WHITEN] = {"type": "conv", "weights": cell(sd["whiten.weight"].t().numpy()[None, None], sd["whiten.bias"].numpy())}
+    mean = np.broadcast_to(sd["preprocess.mean"].numpy().astype(np.float32), (2, 2, 3)).copy()
+    return {"net": {"layers": layers, "meta": {"normalization": {"averageImage": mean}}}}
+
+
+def load_netvlad_mat(path, whiten: bool = True) -> Dict[str, torch.Tensor]:
+    """A NetVLAD checkpoint in the MATLAB struct layout the reference downloads (Pitts30K_struct.mat / TokyoTM_struct.mat, NV:48-51), read as
+    NV:76-121 reads it: HWIO -> OIHW, the score matrix transposed, centres negated, the whitening squeezed and transposed, averageImage[0, 0].
+    K and the whitening width are whatever the file holds.  Validated (validate_netvlad_state) before it is returned."""
+    import numpy as np
+    from scipy.io import loadmat
+
+    mat = loadmat(str(path), struct_as_record=False, squeeze_me=True)
+    layers = mat["net"].layers
+    if len(layers) <= NETVLAD_MAT_WHITEN:
+        raise ValueError(f"NetVLAD: net.layers has {len(layers)} entries, at least {NETVLAD_MAT_WHITEN + 1} expected")
+    f32 = lambda a: torch.tensor(np.asarray(a, dtype=np.float32))  # noqa: E731
+    sd: Dict[str, torch.Tensor] = {}
+    for i, co, ci in NETVLAD_CONVS:
+        w, b = f32(layers[i].weights[0]), f32(layers[i].weights[1])
+        if tuple(w.shape) != (3, 3, ci, co):
+            raise ValueError(f"NetVLAD: tensor 'backbone.{i}.weight' has shape {tuple(w.shape)} in the file, expected (3, 3, {ci}, {co})")
+        sd[f"backbone.{i}.weight"] = w.permute(3, 2, 0, 1).contiguous()
+        sd[f"backbone.{i}.bias"] = b.reshape(-1)
+    score, centers = f32(layers[NETVLAD_MAT_VLAD].weights[0]), -f32(layers[NETVLAD_MAT_VLAD].weights[1])
+    if score.dim() != 2:
+        raise ValueError(f"NetVLAD: tensor 'netvlad.score_proj.weight' has shape {tuple(score.shape)} in the file, expected (512, K)")
+    sd["netvlad.score_proj.weight"] = score.t().contiguous()[:, :, None]
+    sd["netvlad.centers"] = centers.contiguous()
+    if whiten:
+        w, b = f32(layers[NETVLAD_MAT_WHITEN].weights[0]).squeeze(), f32(layers[NETVLAD_MAT_WHITEN].weights[1])
+        if w.dim() != 2:
+            raise ValueError(f"NetVLAD: tensor 'whiten.weight' has shape {tuple(w.shape)} in the file, expected (1, 1, IN, OUT)")
+        sd["whiten.weight"] = w.t().contiguous()
+        sd["whiten.bias"] = b.reshape(-1)
+    sd["preprocess.mean"] = f32(mat["net"].meta.normalization.averageImage[0, 0]).reshape(-1)
+    validate_netvlad_state(sd)
+    return sd

@@ -103,6 +103,7 @@ enum {
   DIM_SAT_ALIKED,         /* ALIKED: inputs of the split-precision convolutions / GEMMs (image, BatchNorm+SELU outputs, SDDH samples) */
   DIM_SAT_ALIKE,          /* ALIKE: activations stored by the encoder / aggregation convolutions, rows and outputs of the head products */
   DIM_SAT_XFEAT,          /* XFeat: the normalised image, block2's input, the pyramid sum and the activations stored by the trunk convolutions */
+  DIM_SAT_NETVLAD,        /* NetVLAD: a NaN pixel, and the activations stored by the thirteen VGG16 convolutions */
   DIM_SAT_SITES = 16
 };
 int dim_saturation_read(unsigned* counts_host, unsigned long long* total, int reset, void* stream);
@@ -318,6 +319,54 @@ int dim_xfeat_extract(dim_xfeat* h, const float* images_dev, int batch, int H, i
 /* Parity taps of the last call: the normalised image and the keypoint heat map K1h [batch][_H][_W], the reliability map [batch][_H/8][_W/8], the
  * L2-normalised dense descriptors [batch][_H/8][_W/8][64], and the resized frame's size. */
 int dim_xfeat_debug_buffers(dim_xfeat* h, const float** norm_image, const float** k1h, const float** h1, const float** m1, int* hr, int* wr);
+
+/* ------------------------------------------------------------------------ */
+/* NetVLAD global descriptor (csrc/netvlad_api.hip, netvlad.hip; NV = thirdparty/hloc/extractors/netvlad.py): the front half of the `retrieval` pair */
+/* strategy.  VGG16 features[:-2] (13 3x3 convolutions, pools after layers 2, 4, 7, 10, no ReLU after the last, NV:66-68) -> per-location L2 -> NetVLAD */
+/* layer with K clusters (NV:18-39) -> optional whitening Linear(512 K -> whiten_out) + L2 (NV:143-144).                                              */
+/* ------------------------------------------------------------------------ */
+
+/* Host pointers, each with its element count (checked against the geometry in create).  conv_w OIHW as NV:86 leaves them (cout, cin, 3, 3) with
+ * channels 3,64 | 64,64 | 64,128 | 128,128 | 128,256 | 256,256 | 256,256 | 256,512 | 512,512 x 5;  score_w (K, 512) = score_proj.weight squeezed (NV:99);
+ * centers (512, K), already negated (NV:95); whiten_w (whiten_out, 512 K), whiten_b (whiten_out) or both NULL with whiten_out 0 (conf "whiten": False);
+ * mean: the checkpoint's averageImage[0, 0] (3 values, NV:118).  K: a multiple of 8 up to 64. */
+typedef struct dim_netvlad_weights {
+  const float* conv_w[13];
+  const float* conv_b[13];
+  size_t conv_w_elems[13], conv_b_elems[13];
+  const float* mean;      size_t mean_elems;
+  const float* score_w;   size_t score_w_elems;
+  const float* centers;   size_t centers_elems;
+  const float* whiten_w;  size_t whiten_w_elems;
+  const float* whiten_b;  size_t whiten_b_elems;
+  int K, whiten_out;
+} dim_netvlad_weights;
+
+typedef struct dim_netvlad dim_netvlad;
+/* max_batch <= 64; max_h, max_w >= 16; max_h x max_w below 2^23 pixels. */
+int dim_netvlad_create(const dim_netvlad_weights* w, int max_batch, int max_h, int max_w, dim_netvlad** out);
+void dim_netvlad_destroy(dim_netvlad* h);
+int dim_netvlad_desc_dim(const dim_netvlad* h);   /* whiten_out, or 512 K without whitening */
+/* images_dev: [batch][H][W][3] fp32 RGB in 0..1 (NV:125; the kernel applies clamp(255 x, 0, 255) - mean, NV:126-130), 16 <= H, W <= the handle's
+ * maximum.  desc_dev: [batch][dim_netvlad_desc_dim] unit-norm rows.  Arithmetic: the convolutions run as fp16x3 (default, range guard DIM_SAT_NETVLAD)
+ * or bf16x6 (dim_tune_set key 1 = 1 or 0) splits on the matrix cores; conv1_1, the head and the whitening are fp32 in every mode.  Every sum has a
+ * fixed order: an image's descriptor does not depend on the batch around it.  Only enqueues work on `stream`.
+ * Images must be finite.  A NaN pixel is read as 0 - mean (the clamp drops it) where the reference returns a NaN descriptor; it bumps DIM_SAT_NETVLAD in
+ * the fp16x3 mode ONLY: the other modes, and therefore the range guard's bf16x6 re-run, have no counter and return a finite descriptor. */
+int dim_netvlad_extract(dim_netvlad* h, const float* images_dev, int batch, int H, int W, float* desc_dev, void* stream);
+/* Parity tap of the last call: the conv5_3 map [batch][mh][mw][512] (fp32, device) the head consumed. */
+int dim_netvlad_debug_buffers(dim_netvlad* h, const float** conv5_map, int* batch, int* mh, int* mw);
+/* The head alone on a conv5_3 map [batch][n][512] (device): per-location L2, scores, softmax, aggregation, intra-normalisation, flatten (d K + k),
+ * global L2 -> vlad_dev [batch][512 K].  score_dk_dev: (512, K) = score_w TRANSPOSED (the checkpoint's own D x K layout); centers_kd_dev: (K, 512) =
+ * centers TRANSPOSED.  workspace: dim_op_netvlad_head_workspace_bytes(batch, n, K) bytes of device memory. */
+size_t dim_op_netvlad_head_workspace_bytes(int batch, int n, int K);
+int dim_op_netvlad_head_f32(const float* map_dev, int batch, int n, int K, const float* score_dk_dev, const float* centers_kd_dev, void* workspace,
+                            float* vlad_dev, void* stream);
+/* The whitening alone: y = normalize(W v + b), v_dev [batch][in_dim], w_dev [out_dim][in_dim], y_dev [batch][out_dim]; in_dim a multiple of 4096.
+ * W is read once per 16 images.  workspace: dim_op_netvlad_whiten_workspace_bytes(batch, in_dim, out_dim) bytes of device memory. */
+size_t dim_op_netvlad_whiten_workspace_bytes(int batch, int in_dim, int out_dim);
+int dim_op_netvlad_whiten_f32(const float* v_dev, int batch, int in_dim, const float* w_dev, const float* bias_dev, int out_dim, void* workspace,
+                              float* y_dev, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* LightGlue (reference LGN:300-610)                                        */
