@@ -12,6 +12,7 @@ matcher_base.py:36-60); otherwise a minimal stand-in base with the same construc
 ``KorniaMatcher`` mirrors matchers/kornia_matcher.py:9-53 (nearest-neighbour descriptor matching, no weights);
 ``SuperPointOpenExtractor`` mirrors extractors/superpoint_open.py:72-164 (the openly licensed SuperPoint);
 ``XfeatExtractor`` mirrors extractors/xfeat.py:11-63 (XFeat's sparse detectAndCompute);
+``RIPEExtractor`` mirrors extractors/ripe.py:10-118 (RIPE, the extractor of the ``ripe+kornia_matcher`` pipeline);
 ``LighterGlueMatcher`` mirrors matchers/lighterglue.py:78-241 (the matcher of the shipped ``xfeat+lighterglue`` pipeline);
 ``SuperGlueMatcher`` mirrors matchers/superglue.py:54-106 (the matcher of the shipped ``superpoint+superglue`` pipeline).
 See INTEGRATION.md for the module files a maintainer adds to the reference tree.
@@ -37,6 +38,7 @@ from .superglue_hip import SuperGlueHIP
 from .superpoint_hip import SuperPointHIP, SuperPointOpenHIP
 from .tile_matching import BatchedTileMatchingMixin
 from .tiling import BatchedTilingMixin
+from .ripe_hip import RipeHIP
 from .xfeat_hip import XFeatHIP
 
 logger = logging.getLogger("dim")
@@ -522,6 +524,59 @@ class XfeatExtractor(_ExtractorBase):
 
     def _frame2tensor(self, image: np.ndarray, device: str = "cuda"):
         """extractors/xfeat.py:44-56."""
+        return _to_device(self, _frame2array(image), device, sync=True)
+
+
+class RIPEExtractor(_ExtractorBase):
+    """extractors/ripe.py:10 — RIPE (vgg_hyper: VGG19-BN encoder, DeDoDe-style decoder, hypercolumn descriptors) on the gfx950 library.  The
+    reference runs its CUDA path under fp16 autocast; this is pinned to its fp32 path.  ``descriptor_size`` says 128 as the reference's class does;
+    the descriptors are 256-dimensional, returned as (256, N)."""
+
+    _default_conf = {  # extractors/ripe.py:11-15
+        "name": "ripe",
+        "max_keypoints": 4000,
+        "detect_threshold": 0.5,
+    }
+    required_inputs = []
+    grayscale = False
+    descriptor_size = 128
+
+    def __init__(self, config):
+        super().__init__(config)
+        self._lib = capi.load()
+        self._device = _resolve_device(self._device, "RIPEExtractor")
+        cfg = self.config.get("extractor")
+        self.max_num_keypoints = int(cfg.get("max_keypoints", self._default_conf["max_keypoints"]))
+        self.detect_threshold = float(cfg.get("detect_threshold", self._default_conf["detect_threshold"]))
+        self._net_cfg = {"top_k": self.max_num_keypoints, "threshold": self.detect_threshold}
+        arith = _apply_arithmetic(cfg, self._lib)
+        if arith is not None:
+            self._net_cfg["arithmetic"] = arith
+        self._net_cfg["on_saturation"] = _saturation_policy(cfg)
+        path = cfg.get("weights_path") or os.environ.get("DIM_RIPE_WEIGHTS")
+        if path is None and cfg.get("allow_synthetic_weights"):
+            logger.warning("RIPE: running on seeded SYNTHETIC weights (allow_synthetic_weights) - test / benchmark use only")
+        self._sd = _weights.load_ripe_state_dict(path, allow_synthetic=bool(cfg.get("allow_synthetic_weights", False)))
+        self._net: Optional[RipeHIP] = None
+        self._net_hw = (0, 0)
+
+    def _ensure(self, H: int, W: int):
+        if self._net is None or H > self._net_hw[0] or W > self._net_hw[1]:
+            hw = (max(H, self._net_hw[0]), max(W, self._net_hw[1]))
+            self._net = RipeHIP(self._sd, self._net_cfg, max_batch=1, max_hw=hw, device=self._device, lib=self._lib)
+            self._net_hw = hw
+
+    @torch.no_grad()
+    def _extract(self, image: np.ndarray) -> dict:
+        """image: HxWx3 or HxW, 0..255 (extractors/ripe.py:57-89).  Returns numpy keypoints (N,2), descriptors (256,N), scores (N,);
+        RuntimeError("No keypoints detected") where the reference raises it."""
+        t = self._frame2tensor(image, self._device)          # [1, C, H, W] in 0..1
+        self._ensure(t.shape[2], t.shape[3])
+        f = self._net(t)
+        return {"keypoints": f["keypoints"].cpu().numpy(), "descriptors": f["descriptors"].cpu().numpy().T, "scores": f["scores"].cpu().numpy()}
+
+    def _frame2tensor(self, image: np.ndarray, device: str = "cuda"):
+        """extractors/ripe.py:91-112."""
         return _to_device(self, _frame2array(image), device, sync=True)
 
 

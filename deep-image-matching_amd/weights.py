@@ -793,3 +793,114 @@ def load_netvlad_mat(path, whiten: bool = True) -> Dict[str, torch.Tensor]:
     sd["preprocess.mean"] = f32(mat["net"].meta.normalization.averageImage[0, 0]).reshape(-1)
     validate_netvlad_state(sd)
     return sd
+
+
+# ---- RIPE (thirdparty/RIPE/ripe: model_zoo/vgg_hyper.py, models/backbones/vgg.py, vgg_utils.py; checkpoint ripe_weights.pth) ------------------
+# vgg19_bn().features[:40]: index of every 3x3 convolution in the Sequential (its BatchNorm sits at index + 1), cout, cin; pools at 6, 13, 26, 39
+RIPE_ENCODER = [(0, 64, 3), (3, 64, 64), (7, 128, 64), (10, 128, 128), (14, 256, 128), (17, 256, 256), (20, 256, 256), (23, 256, 256),
+                (27, 512, 256), (30, 512, 512), (33, 512, 512), (36, 512, 512)]
+# ConvRefiner per decoder scale (vgg.py:38-71, mode "dect"): scale, in, hidden, out
+RIPE_DECODER = [("8", 512, 512, 257), ("4", 512, 256, 129), ("2", 256, 128, 65), ("1", 128, 64, 2)]
+RIPE_HIDDEN_BLOCKS = 8
+RIPE_HYPER_DIM, RIPE_DESC_DIM = 960, 256
+RIPE_BN_EPS = 1e-5
+_RIPE_BN = (("weight", False), ("bias", False), ("running_mean", False), ("running_var", False), ("num_batches_tracked", True))
+
+
+def _ripe_layout():
+    t = []
+
+    def bn(p, c):
+        return [(f"{p}.{s}", () if scalar else (c,)) for s, scalar in _RIPE_BN]
+
+    for i, co, ci in RIPE_ENCODER:
+        t += [(f"net.encoder.layers.{i}.weight", (co, ci, 3, 3)), (f"net.encoder.layers.{i}.bias", (co,))] + bn(f"net.encoder.layers.{i + 1}", co)
+    for s, cin, hid, out in RIPE_DECODER:
+        p = f"net.decoder.layers.{s}"
+        t += [(f"{p}.block1.0.weight", (hid, cin, 1, 1)), (f"{p}.block1.0.bias", (hid,))] + bn(f"{p}.block1.1", hid)
+        t += [(f"{p}.block1.3.weight", (hid, hid, 1, 1)), (f"{p}.block1.3.bias", (hid,))]
+        for j in range(RIPE_HIDDEN_BLOCKS):
+            q = f"{p}.hidden_blocks.{j}"
+            t += [(f"{q}.0.weight", (hid, 1, 5, 5)), (f"{q}.0.bias", (hid,))] + bn(f"{q}.1", hid)
+            t += [(f"{q}.3.weight", (hid, hid, 1, 1)), (f"{q}.3.bias", (hid,))]
+        t += [(f"{p}.out_conv.weight", (out, hid, 1, 1)), (f"{p}.out_conv.bias", (out,))]
+    t += [("conv_dim_reduction_coarse_desc.weight", (RIPE_DESC_DIM, RIPE_HYPER_DIM, 1)), ("conv_dim_reduction_coarse_desc.bias", (RIPE_DESC_DIM,))]
+    return t
+
+
+RIPE_LAYOUT = _ripe_layout()   # (key, shape) of every tensor of vgg_hyper()'s state dict
+
+
+def validate_ripe_state_dict(sd: Dict[str, torch.Tensor]) -> None:
+    """KeyError for a missing / unexpected tensor, ValueError for a wrong shape, a non-finite value or a negative running_var — each naming the
+    tensor — before anything native is called.  ``num_batches_tracked`` is accepted and ignored, present or not."""
+    table = dict(RIPE_LAYOUT)
+    for k, shape in RIPE_LAYOUT:
+        if k not in sd:
+            if k.endswith("num_batches_tracked"):
+                continue
+            raise KeyError(f"RIPE: state dict has no tensor {k!r}")
+        if k.endswith("num_batches_tracked"):
+            continue
+        if tuple(sd[k].shape) != tuple(shape):
+            raise ValueError(f"RIPE: tensor {k!r} has shape {tuple(sd[k].shape)}, expected {tuple(shape)}")
+        if not bool(torch.isfinite(sd[k]).all()):
+            raise ValueError(f"RIPE: tensor {k!r} holds a non-finite value")
+        if k.endswith("running_var") and not bool((sd[k] >= 0).all()):
+            raise ValueError(f"RIPE: tensor {k!r} has a negative entry")
+    for k in sd:
+        if k not in table:
+            raise KeyError(f"RIPE: unexpected tensor {k!r} in the state dict")
+
+
+def fold_ripe_batchnorm(sd: Dict[str, torch.Tensor], conv: str, bn: str, dtype=torch.float64):
+    """(weight, bias) of the convolution ``conv`` with the eval-mode BatchNorm ``bn`` behind it folded in, evaluated in ``dtype``:
+    w' = w gamma / sqrt(var + eps) per output channel, b' = (b - mean) gamma / sqrt(var + eps) + beta — what dim_ripe_create does in fp64."""
+    sc = sd[f"{bn}.weight"].to(dtype) / torch.sqrt(sd[f"{bn}.running_var"].to(dtype) + RIPE_BN_EPS)
+    w = sd[f"{conv}.weight"].to(dtype)
+    return w * sc.reshape(-1, *([1] * (w.dim() - 1))), (sd[f"{conv}.bias"].to(dtype) - sd[f"{bn}.running_mean"].to(dtype)) * sc + sd[f"{bn}.bias"].to(dtype)
+
+
+def synthetic_ripe_state_dict(seed: int = 41, logit_gain: float = 0.035, logit_bias: float = 0.2125) -> Dict[str, torch.Tensor]:
+    """Seeded synthetic RIPE weights under the reference's own keys.  He-normal convolutions (the depthwise ones over their 25 taps) with 0.1 N(0, 1)
+    biases; BatchNorm running means 0.2 N(0, 1), running variances U(0.5, 1.5), betas 0.1 N(0, 1) and gammas U(0.6, 1.4) of which every seventh
+    channel is negated: the statistics are not the identity and a folded scale can be negative.  The pointwise convolution that closes a hidden
+    block is scaled by 1 / sqrt(2), so the eight blocks keep the hidden tensor's second moment.  Row 0 of every out_conv (the logit channel) is
+    scaled by ``logit_gain`` and biased by ``logit_bias``: the four scales then add up to a heat map whose 3 x 3 maxima lie on both sides of the
+    reference's detect threshold 0.5 on noise images."""
+    g = torch.Generator().manual_seed(seed)
+    sd: Dict[str, torch.Tensor] = {}
+    for k, shape in RIPE_LAYOUT:
+        if k.endswith("num_batches_tracked"):
+            sd[k] = torch.tensor(0)
+        elif k.endswith("running_var"):
+            sd[k] = 0.5 + torch.rand(shape, generator=g)
+        elif k.endswith("running_mean"):
+            sd[k] = 0.2 * torch.randn(shape, generator=g)
+        elif len(shape) == 1 and k.endswith(".weight"):   # only a BatchNorm has a one-dimensional weight
+            gamma = 0.6 + 0.8 * torch.rand(shape, generator=g)
+            gamma[3::7] *= -1.0
+            sd[k] = gamma
+        elif len(shape) == 1:
+            sd[k] = 0.1 * torch.randn(shape, generator=g)
+        else:
+            fan_in = shape[1] * (shape[2] * shape[3] if len(shape) == 4 else 1)
+            sd[k] = torch.randn(shape, generator=g) * math.sqrt(2.0 / fan_in)
+            if ".hidden_blocks." in k and k.endswith(".3.weight"):
+                sd[k] *= math.sqrt(0.5)
+    for s, *_ in RIPE_DECODER:
+        sd[f"net.decoder.layers.{s}.out_conv.weight"][0] *= logit_gain
+        sd[f"net.decoder.layers.{s}.out_conv.bias"][0] = logit_bias
+    return sd
+
+
+def load_ripe_state_dict(path: str | None = None, seed: int = 41, allow_synthetic: bool = False) -> Dict[str, torch.Tensor]:
+    """ripe_weights.pth (the state dict model_zoo/vgg_hyper.py loads into RIPE(VGG, HyperColumnFeatures)), validated against RIPE_LAYOUT.
+    ``path``: a file name or an open binary file."""
+    if path is None:
+        _no_weights("RIPE (ripe_weights.pth, thirdparty/RIPE/ripe/model_zoo/vgg_hyper.py)", "DIM_RIPE_WEIGHTS", allow_synthetic)
+        return synthetic_ripe_state_dict(seed)
+    sd = torch.load(path if hasattr(path, "read") else str(Path(path)), map_location="cpu")
+    sd = {k: (v.float().contiguous() if v.is_floating_point() else v) for k, v in sd.items()}
+    validate_ripe_state_dict(sd)
+    return sd

@@ -80,7 +80,10 @@ enum {
   DIM_PROF_SP_CONV3B, DIM_PROF_SP_CONV4A, DIM_PROF_SP_CONV4B, DIM_PROF_SP_CONVPA, DIM_PROF_SP_CONVPB,
   DIM_PROF_SP_CONVDA, DIM_PROF_SP_CONVDB, DIM_PROF_SP_POST, DIM_PROF_LG_SELF_ATTN, DIM_PROF_LG_CROSS_ATTN,
   DIM_PROF_LG_GEMMS, DIM_PROF_LG_ASSIGN,
-  DIM_PROF_AL_CONV_FULL   /* ALIKED's full-resolution 3x3 convolutions (block1.conv1 3 -> 16, block1.conv2 16 -> 16): HBM-bound */
+  DIM_PROF_AL_CONV_FULL,  /* ALIKED's full-resolution 3x3 convolutions (block1.conv1 3 -> 16, block1.conv2 16 -> 16): HBM-bound */
+  /* dim_ripe_extract in seven spans: statistics + encoder, the decoder's scales 8 / 4 / 2 / 1 (DEC8 + d; each with the resizes that follow it),
+   * detection (maxima, map maximum, selection), descriptors (sampling, 960 -> 256, normalisation) */
+  DIM_PROF_RIPE_ENCODER, DIM_PROF_RIPE_DEC8, DIM_PROF_RIPE_DEC4, DIM_PROF_RIPE_DEC2, DIM_PROF_RIPE_DEC1, DIM_PROF_RIPE_DETECT, DIM_PROF_RIPE_DESC
 };
 int dim_profile_start(unsigned long long site_mask);
 int dim_profile_stop(double* total_ms, int* launches);
@@ -104,6 +107,7 @@ enum {
   DIM_SAT_ALIKE,          /* ALIKE: activations stored by the encoder / aggregation convolutions, rows and outputs of the head products */
   DIM_SAT_XFEAT,          /* XFeat: the normalised image, block2's input, the pyramid sum and the activations stored by the trunk convolutions */
   DIM_SAT_NETVLAD,        /* NetVLAD: a NaN pixel, and the activations stored by the thirteen VGG16 convolutions */
+  DIM_SAT_RIPE,           /* RIPE: a non-finite pixel, and the activations stored by the encoder and decoder convolutions */
   DIM_SAT_SITES = 16
 };
 int dim_saturation_read(unsigned* counts_host, unsigned long long* total, int reset, void* stream);
@@ -367,6 +371,63 @@ int dim_op_netvlad_head_f32(const float* map_dev, int batch, int n, int K, const
 size_t dim_op_netvlad_whiten_workspace_bytes(int batch, int in_dim, int out_dim);
 int dim_op_netvlad_whiten_f32(const float* v_dev, int batch, int in_dim, const float* w_dev, const float* bias_dev, int out_dim, void* workspace,
                               float* y_dev, void* stream);
+
+/* ------------------------------------------------------------------------ */
+/* RIPE (thirdparty/RIPE/ripe: model_zoo/vgg_hyper.py, models/ripe.py = RPM, models/backbones/vgg.py = RPV, vgg_utils.py = RPU,                        */
+/* backbone_base.py = RPB, models/upsampler/hypercolumn_features.py = RPH) as extractors/ripe.py drives it: InstanceNorm2d(3) -> VGG19-BN features[:39]  */
+/* (twelve conv + BN + ReLU, the map in front of each of the four pools kept) -> DeDoDe-style decoder at scales 8, 4, 2, 1 (ConvRefiner: 1x1, BN, ReLU,  */
+/* 1x1; eight depthwise 5x5 + BN + ReLU + 1x1 blocks; (x + x0) / 1.4; 1x1) with bilinear resizes between them -> heat map -> 3x3 maximum + threshold +    */
+/* top-k -> hypercolumn rows (960) of the keypoints -> Conv1d(960, 256) -> L2.                                                                         */
+/* ------------------------------------------------------------------------ */
+
+/* One convolution followed by an eval-mode BatchNorm (eps 1e-5), host pointers: w, b of the convolution, the BatchNorm's weight, bias, running_mean,
+ * running_var.  Folded in fp64 at create time. */
+typedef struct dim_ripe_convbn { const float *w, *b, *gamma, *beta, *mean, *var; } dim_ripe_convbn;
+/* ConvRefiner of one scale (RPU:32-102): block1 = conv0 (hidden, in, 1, 1) + BN, conv3 (hidden, hidden, 1, 1); hidden_blocks[j] = depthwise
+ * (hidden, 1, 5, 5) + BN, pointwise (hidden, hidden, 1, 1); out_conv (out, hidden, 1, 1).  (in, hidden, out) = (512, 512, 257), (512, 256, 129),
+ * (256, 128, 65), (128, 64, 2) at scales 8, 4, 2, 1. */
+typedef struct dim_ripe_refiner {
+  dim_ripe_convbn block1_0;
+  const float *block1_3_w, *block1_3_b;
+  dim_ripe_convbn dw[8];
+  const float *pw_w[8], *pw_b[8];
+  const float *out_w, *out_b;
+} dim_ripe_refiner;
+/* enc[i]: the i-th 3x3 convolution (cout, cin, 3, 3) of torchvision's vgg19_bn with its BatchNorm, channels 3,64 | 64,64 | 64,128 | 128,128 | 128,256 |
+ * 256,256 x 3 | 256,512 | 512,512 x 3.  dec[0..3]: scales 8, 4, 2, 1.  desc_w (256, 960), desc_b (256): conv_dim_reduction_coarse_desc. */
+typedef struct dim_ripe_weights {
+  dim_ripe_convbn enc[12];
+  dim_ripe_refiner dec[4];
+  const float *desc_w, *desc_b;
+} dim_ripe_weights;
+
+typedef struct dim_ripe dim_ripe;
+/* max_batch <= 64; max_h, max_w >= 16; max_h x max_w below 2^23 pixels; capacity (rows of the output tables per image) in [1, 32768]. */
+int dim_ripe_create(const dim_ripe_weights* w, int max_batch, int max_h, int max_w, int capacity, dim_ripe** out);
+void dim_ripe_destroy(dim_ripe* h);
+/* RIPE.detectAndCompute (RPM:201-260) on images_dev [batch][H][W][3] fp32 RGB in 0..1 (a gray image repeated to three channels, RPB:55-59),
+ * 16 <= H, W <= the handle's maximum.  0 < top_k <= capacity, threshold >= 0 (the key map marks "no candidate" with 0).  Per image b, n = counts_dev[b]
+ * rows in descending score, ties by ascending pixel index y W + x: kpts_xy_dev [batch][capacity][2] integer pixel positions (x, y), scores_dev
+ * [batch][capacity] = heat / max of the whole heat map, desc_dev [batch][capacity][256] unit-norm rows; rows past n are zero (descriptors, scores) or
+ * unspecified (keypoints).  counts_dev[b] == 0 is where the reference raises "No keypoints detected": the caller decides.
+ * Arithmetic: the eleven 64..512-channel 3x3 convolutions and every 1x1 convolution run as fp16x3 (default, range guard DIM_SAT_RIPE) or bf16x6
+ * (dim_tune_set key 1 = 1 or 0) splits on the matrix cores; the first layer, the depthwise convolutions, the resizes, the detection and the sampling are
+ * fp32 in every mode.  Every sum has a fixed order: an image's result does not depend on the batch around it.  Only enqueues work on `stream`. */
+int dim_ripe_extract(dim_ripe* h, const float* images_dev, int batch, int H, int W, int top_k, float threshold, float* kpts_xy_dev, float* scores_dev,
+                     float* desc_dev, int32_t* counts_dev, void* stream);
+/* Parity taps of the last call (fp32, device): heat [batch][H][W]; maps[l] [batch][hs[l]][ws[l]][64 << l], l = 0..3 (the encoder maps in front of the pools). */
+int dim_ripe_debug_buffers(dim_ripe* h, const float** heat, const float** maps4, int* hs4, int* ws4, int* batch);
+/* The new kernels alone (device pointers, fp32):
+ *  dim_op_ripe_dw5x5_f32            out = relu(depthwise5x5(in, pad 2) + bias): in / out [batch][H][W][C], w [25 = 5 dy + dx][C] (BatchNorm folded), C % 32 == 0
+ *  dim_op_ripe_resize_bilinear_f32  F.interpolate(bilinear, align_corners=False): channels [c_off, c_off + C) of in [batch][h][w][ld] -> out [batch][H][W][C]
+ *  dim_op_ripe_nms3_f32             key [batch][H][W] = heat where it equals its 3x3 window maximum and exceeds threshold (>= 0), else 0
+ *  dim_op_ripe_hypercolumn_f32      rows [batch][capacity][960] of the first n_kpts[b] keypoints (x, y) of kpts [batch][capacity][2]: grid_sample
+ *                                   (bilinear, align_corners=True, zero padding) of maps4[l] [batch][hs4[l]][ws4[l]][64 << l] at 2 (x, y) / (W - 1, H - 1) - 1 */
+int dim_op_ripe_dw5x5_f32(const float* in_dev, const float* w_dev, const float* bias_dev, float* out_dev, int batch, int H, int W, int C, void* stream);
+int dim_op_ripe_resize_bilinear_f32(const float* in_dev, int ld, int c_off, int C, int batch, int h, int w, float* out_dev, int H, int W, void* stream);
+int dim_op_ripe_nms3_f32(const float* heat_dev, float* key_dev, float threshold, int batch, int H, int W, void* stream);
+int dim_op_ripe_hypercolumn_f32(const float* const* maps4, const int* hs4, const int* ws4, const float* kpts_dev, const int32_t* n_kpts_dev, float* rows_dev,
+                                int capacity, int batch, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* LightGlue (reference LGN:300-610)                                        */
